@@ -1,6 +1,13 @@
 """bench.py — Gibbs sweeps/s of the MI355X sampler (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(headline, roofline of the timed steps).  --dump-outputs DIR also writes the
+chain state after the last timed step as DIR/<name>.npy.  Everything else
+the benchmark measures (per-phase kernel times and the pooled hyperparameter
+means from sweeps of their own, the CPU baseline, the `extra` legs) runs
+only with --full.
 
 Workload (BASELINE.json configs[3], one shard per GPU): synthetic data
 N = 1,000,000 customers, V = 4 views, D = 128 dims, K = 64 generating
@@ -17,8 +24,8 @@ bracketed by barrier + device sync and the max over ranks is reported.
 
 Output: one JSON line on rank 0 (driver contract), including the roofline of
 the dominant kernel (zresample) measured with HIP events on the sampler's
-stream, and a CPU baseline (the oracle's restatement of the same chain, one
-full sweep on one host core).  With N = 1 it also reports (key `extra`) the
+stream, and with --full a CPU baseline (the oracle's restatement of the same
+chain, one full sweep on one host core).  With --full and N = 1 it also reports (key `extra`) the
 GPU on the north_star literal (D = 1) and configs[1], the exact schedule on
 configs[0], a cold start on configs[1], and the reference's algorithm
 (oracle ExactSampler, libm) on the host at the north_star literal.
@@ -59,15 +66,41 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c4", choices=sorted(CONFIGS))
     ap.add_argument("--seed", type=int, default=1999)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the per-phase kernel times, the pooled hyperparameter "
+                         "means, the CPU baseline and the extra legs (a plain run skips all of these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the chain state after the last timed step (table_of, dish_of, hyper, dish_counts) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU legs")
     ap.add_argument("--shard", action="store_true",
                     help="N > 1: ONE chain split over the N GPUs (within-chain N-sharding of phase A, an RCCL "
                          "all-gather of the choices per sweep; strong scaling) instead of one chain per GPU")
     ap.add_argument("--leg", default=None, help=argparse.SUPPRESS)   # child_leg: run one multi-chain leg, print it
     ap.add_argument("--leg-device", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra lines (other configs, exact schedule, cold start, reference CPU)")
+                    help="with --full: skip the extra lines (other configs, exact schedule, cold start, "
+                         "reference CPU)")
     return ap.parse_args()
+
+
+DUMP_MAX_BYTES = 48 << 20    # per array; the whole dump stays under 64 MB
+
+
+def dump_outputs(path, s, suffix=""):
+    """The state a caller of the timed path reads back after its last step
+    (Sampler.state / dish_counts), one float64 .npy per array: table_of[n]
+    (a fixed seeded sample of the customers, in ascending order, where all n
+    would exceed DUMP_MAX_BYTES), dish_of[V][T], hyper = tau_v, alpha_v,
+    sigma_v, alpha_global, sigma_global, and dish_counts[V]."""
+    os.makedirs(path, exist_ok=True)
+    table_of, dish_of, h = s.state()
+    if table_of.size * 8 > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(table_of.size, DUMP_MAX_BYTES // 8, replace=False))
+        table_of = table_of[keep]
+    hyper = np.concatenate([h["tau_v"], h["alpha_v"], h["sigma_v"], [h["alpha_global"], h["sigma_global"]]])
+    for name, a in (("table_of", table_of), ("dish_of", dish_of), ("hyper", hyper), ("dish_counts", s.dish_counts())):
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), np.asarray(a, dtype=np.float64))
 
 
 def warm_state(z, V, K):
@@ -433,7 +466,7 @@ def main():
     t_gen = time.perf_counter() - t_gen
     # coarse timing in the timed region: HIP events around the z-resample pass
     # (the roofline) and the sweep only; the per-phase breakdown is taken on
-    # extra sweeps after the timed region (each event pair idles the GPU ~5 us)
+    # extra sweeps after the timed region, with --full (each event pair idles the GPU ~5 us)
     if y is not None:
         s = Sampler(y, seed=args.seed, mode="parallel", first_chain=0 if shard else rank, device=local,
                     timing="coarse")
@@ -459,37 +492,40 @@ def main():
         elapsed = float(t.item())
 
     kms, kcnt = s.kernel_time("zresample")
-    sweep_ms, _ = s.kernel_time("sweep")
-    # posterior-mean accumulators over 10 more saved sweeps (after the timed
-    # region), reduced across ranks with R-hat
-    from mvc_amd import dist as mdist
-    s.set_timing(False)
-    cstats = mdist.ChainStats(3 * V + 2)
-    for _ in range(10):
-        s.sweep(1)
-        _, _, h = s.state()
-        hv = np.concatenate([h["alpha_v"], h["sigma_v"], h["tau_v"], [h["alpha_global"], h["sigma_global"]]])
-        if not (shard and rank != 0):   # a sharded chain is counted once
-            cstats.add(0, hv)
-    n_detail = 3
-    s.set_timing(True)
-    s.reset_timers()
-    s.sweep(n_detail)
-    s.synchronize()
-    parts = {k: s.kernel_time(k)[0] / n_detail
-             for k in ("zresample", "lp", "draw", "repair", "hyper")}
-    repair = s.repair_stats()
+    if args.dump_outputs:   # the state after the last timed step, every rank its own chain
+        dump_outputs(args.dump_outputs, s, "" if world == 1 else f"_rank{rank}")
+    if args.full:
+        # posterior-mean accumulators over 10 more saved sweeps (after the timed
+        # region), reduced across ranks with R-hat
+        from mvc_amd import dist as mdist
+        s.set_timing(False)
+        cstats = mdist.ChainStats(3 * V + 2)
+        for _ in range(10):
+            s.sweep(1)
+            _, _, h = s.state()
+            hv = np.concatenate([h["alpha_v"], h["sigma_v"], h["tau_v"], [h["alpha_global"], h["sigma_global"]]])
+            if not (shard and rank != 0):   # a sharded chain is counted once
+                cstats.add(0, hv)
+        n_detail = 3
+        s.set_timing(True)
+        s.reset_timers()
+        s.sweep(n_detail)
+        s.synchronize()
+        parts = {k: s.kernel_time(k)[0] / n_detail
+                 for k in ("zresample", "lp", "draw", "repair", "hyper")}
+        repair = s.repair_stats()
     kdish = s.dish_counts()
     _, dish_now, hyper_now = s.state()
     T = dish_now.shape[1]
     zpath = s.zpath()
     s.close()
 
-    # the cross-chain reduce of the hyperparameter accumulators (one
-    # all-reduce over RCCL, outside the timed region; reported, never fed
-    # back: DESIGN.md §7)
-    red = cstats.reduce(device=f"cuda:{local}" if dist is not None else None)
-    pooled_mean = red["mean"]
+    if args.full:
+        # the cross-chain reduce of the hyperparameter accumulators (one
+        # all-reduce over RCCL, outside the timed region; reported, never fed
+        # back: DESIGN.md §7)
+        red = cstats.reduce(device=f"cuda:{local}" if dist is not None else None)
+        pooled_mean = red["mean"]
 
     if rank != 0:
         if dist is not None:
@@ -539,16 +575,18 @@ def main():
                                 else "mfma" if (zpath & 3) == 2 else "mfma-dish-blocks" if zpath & 64
                                 else "generic"),
                 "draw": "registers" if zpath & 4 else "lds-checkpoints"},
-        "hyper_pooled": {"chains": red["chains"], "draws": red["count"],
-                         "alpha_global": round(float(pooled_mean[-2]), 6),
-                         "sigma_global": round(float(pooled_mean[-1]), 6),
-                         "rhat_max": None if red["rhat"] is None else round(float(np.nanmax(red["rhat"])), 4)},
         "nvk_sweeps_per_s": round(value * N * V * K, 1),
-        "kernel_ms_per_sweep": {k: round(v, 4) for k, v in parts.items()},
-        "repair_last_sweep": repair,
-        "kernel_ms_note": "per-phase HIP-event times from 3 sweeps after the timed region",
         "data_gen_s": round(t_gen, 2),
     }
+    if args.full:
+        out["hyper_pooled"] = {"chains": red["chains"], "draws": red["count"],
+                               "alpha_global": round(float(pooled_mean[-2]), 6),
+                               "sigma_global": round(float(pooled_mean[-1]), 6),
+                               "rhat_max": None if red["rhat"] is None else round(float(np.nanmax(red["rhat"])), 4)}
+        out["kernel_ms_per_sweep"] = {k: round(v, 4) for k, v in parts.items()}
+        out["repair_last_sweep"] = repair
+        out["kernel_ms_note"] = "per-phase HIP-event times from 3 sweeps after the timed region"
+
     def leg(name, fn, *a):
         """A host-side leg (CPU only); an exception is recorded, not raised."""
         t = time.perf_counter()
@@ -560,9 +598,9 @@ def main():
         return r
 
     # the headline's CPU baseline first (host only), then the extras
-    if world == 1 and not args.no_cpu_baseline and y is not None:
+    if args.full and world == 1 and not args.no_cpu_baseline and y is not None:
         out["cpu_baseline"] = leg("cpu_baseline", cpu_baseline, y, z, V, K, D, args.seed)
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         # other BASELINE configs and schedules, after the timed region (rank 0,
         # N = 1), each GPU leg in its own process so that no failure there can
         # reach this process's line

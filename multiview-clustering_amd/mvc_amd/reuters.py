@@ -2,7 +2,9 @@
 
 The three count views of dataset/reuters/data pre-process.R:50-108 (body DTM,
 title DTM, binary <D> values) are built by scripts/reuters_build.py and
-committed as CSR counts (reuters_counts.npz, 2.3 MB).  The R script stops at
+committed as CSR counts under tests/golden/reuters/ (reuters_counts.npz and
+the body view's column indices in BODY_PARTS pieces, every file below
+1 MiB; 2.3 MB in all).  The R script stops at
 the count matrices (it never calls the sampler); feeding them to the Gaussian
 sampler is this build's choice:
 
@@ -31,22 +33,41 @@ import os
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-COUNTS = os.path.join(_HERE, "reuters_counts.npz")
+DATA_DIR = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "tests", "golden", "reuters")
+COUNTS = os.path.join(DATA_DIR, "reuters_counts.npz")
+BODY_PARTS = 3
+
+
+def body_part(k, data_dir=DATA_DIR):
+    """File of piece k of body_indices (consecutive slices, np.array_split)."""
+    return os.path.join(data_dir, f"reuters_body_indices_{k}.npz")
+
+
+def _load():
+    """Every array of the committed counts by name; body_indices joined from its pieces."""
+    with np.load(COUNTS) as z:
+        d = {k: z[k] for k in z.files}
+    parts = []
+    for k in range(BODY_PARTS):
+        with np.load(body_part(k)) as p:
+            parts.append(p["body_indices"])
+    d["body_indices"] = np.concatenate(parts)
+    return d
 
 
 def _csr(z, name, ncol):
     from scipy.sparse import csr_matrix
     indptr = z[f"{name}_indptr"]
     indices = z[f"{name}_indices"]
-    data = z[f"{name}_data"] if f"{name}_data" in z.files else np.ones(indices.size, np.uint16)
+    data = z[f"{name}_data"] if f"{name}_data" in z else np.ones(indices.size, np.uint16)
     return csr_matrix((data.astype(np.float64), indices, indptr), shape=(indptr.size - 1, int(ncol)))
 
 
 def counts():
     """(body, title, topics) count matrices (scipy CSR, documents x terms)."""
-    with np.load(COUNTS) as z:
-        return (_csr(z, "body", z["body_terms"]), _csr(z, "title", z["title_terms"]),
-                _csr(z, "topics", z["topics_terms"]))
+    z = _load()
+    return (_csr(z, "body", z["body_terms"]), _csr(z, "title", z["title_terms"]),
+            _csr(z, "topics", z["topics_terms"]))
 
 
 def topics_columns():

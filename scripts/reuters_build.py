@@ -28,6 +28,7 @@ import glob
 import os
 import re
 import string
+import sys
 
 import numpy as np
 
@@ -109,8 +110,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--src", default="/root/reference/dataset/reuters/reuters21578")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                                                  "multiview-clustering_amd", "mvc_amd", "reuters_counts.npz"))
+                                                  "tests", "golden", "reuters"),
+                    help="directory of reuters_counts.npz and the body_indices pieces (mvc_amd.reuters reads them)")
     a = ap.parse_args()
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                    "multiview-clustering_amd"))
+    from mvc_amd import reuters
     docs = read_docs(a.src)
     (bp, bi, bd), bv = dtm([d["body"] for d in docs], 5)
     (tp, ti, td), tv = dtm([d["title"] for d in docs], 3)
@@ -126,16 +131,23 @@ def main():
     for d in docs:
         li.extend(tcol[x] for x in d["topics"])
         lp.append(len(li))
+    os.makedirs(a.out, exist_ok=True)
+    files = [os.path.join(a.out, os.path.basename(reuters.COUNTS))]
+    # body_indices is the bulk of the data: kept apart, in pieces, so that no file exceeds 1 MiB
+    for k, piece in enumerate(np.array_split(bi, reuters.BODY_PARTS)):
+        files.append(reuters.body_part(k, a.out))
+        np.savez_compressed(files[-1], body_indices=piece)
     np.savez_compressed(
-        a.out,
+        files[0],
         ids=np.array([d["id"] for d in docs], np.int32),
-        body_indptr=bp, body_indices=bi, body_data=bd, body_terms=np.array(len(bv)),
+        body_indptr=bp, body_data=bd, body_terms=np.array(len(bv)),
         title_indptr=tp, title_indices=ti, title_data=td, title_terms=np.array(len(tv)),
         topics_indptr=np.array(kp, np.int64), topics_indices=np.array(ki, np.int32), topics_terms=np.array(len(dvocab)),
         label_indptr=np.array(lp, np.int64), label_indices=np.array(li, np.int32),
         label_names=np.array(tvocab), topics_names=np.array(dvocab))
     print(f"{len(docs)} documents; body {len(bv)} terms ({bi.size} nonzeros), title {len(tv)} terms, "
-          f"<D> values {len(dvocab)}, TOPICS values {len(tvocab)} -> {a.out} ({os.path.getsize(a.out) / 1e6:.1f} MB)")
+          f"<D> values {len(dvocab)}, TOPICS values {len(tvocab)} -> {a.out} "
+          f"({len(files)} files, the largest {max(os.path.getsize(f) for f in files) / 1e6:.2f} MB)")
 
 
 if __name__ == "__main__":
