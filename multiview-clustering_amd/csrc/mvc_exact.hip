@@ -1019,6 +1019,7 @@ class ExactSampler : public Sampler {
   double *y_dev = nullptr;
   std::vector<ExactAlloc> chains;
   ExactChain *chains_dev = nullptr;
+  const PathOpts opts = parse_path_opts();   // MVC_PATH, read at creation
 
   ExactSampler(const mvc_config &c, const double *const *views) {
     cfg = c;
@@ -1253,7 +1254,7 @@ class ExactSampler : public Sampler {
       part = std::max(part, (size_t)((char *)A.h.mhbuf - (char *)A.h.n_t));
     }
     int m = full <= kExactLds ? 2 : (part <= kExactLds ? 1 : 0);
-    if (const char *e = path_opt("exact_lds"); e && e[0] >= '0' && e[0] <= '2') m = std::min(m, e[0] - '0');   // tests (MVC_PATH)
+    m = std::min(m, opts.exact_lds);   // tests (MVC_PATH exact_lds)
     if (mode) *mode = m;
     return (int)(m == 2 ? full : (m == 1 ? part : 0));
   }

@@ -6,9 +6,9 @@
 #include <stdint.h>
 
 #include "mvc_philox.h"
+#include "mvc_plan.h"   // MVC_MAXV, and the constants / LDS sizes the host's path decisions share with the kernels
 #include "mvc_pmath.h"
 
-#define MVC_MAXV 64          // max views handled in LDS-resident scalars
 #define MVC_WAVE 64          // CDNA wavefront
 
 // ---------------------------------------------------------------------------

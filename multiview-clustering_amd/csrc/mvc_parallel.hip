@@ -73,8 +73,7 @@ typedef double mvc_d4 __attribute__((ext_vector_type(4)));
 //      dishes and tables (the spec of oracle eval_view_seq /
 //      resample_customer), no cross-lane traffic.
 // ---------------------------------------------------------------------------
-#define MVC_Z_KMAX 64
-#define MVC_Z_VMAX 8
+// (MVC_Z_KMAX, MVC_Z_VMAX and the kernels' LDS size functions: mvc_plan.h)
 
 // Within a slab, customer row rho sits at slot 4 (rho & 3) + (rho >> 2): the
 // rows one lane of the MFMA producer holds (grp, grp + 4, grp + 8, grp + 12 of
@@ -153,10 +152,6 @@ typedef double mvc_d2 __attribute__((ext_vector_type(2)));
 // pairs ahead (across tile boundaries), so HBM latency hides behind 2 RP
 // k-steps of every wave on the CU.  The tile's lp goes straight from the
 // accumulators to the lp buffer (a fixed number of stores per tile).
-#define MVC_ZR 8              // SP (k-steps per view) is padded to a multiple of this
-__host__ __device__ inline size_t lpview_shared_bytes(int SP, int NT, int K, int T) {
-  return 8 * ((size_t)SP * NT * 64 + 3 * (size_t)K + 8 * 48) + 4 * (2 * (size_t)K + 2 * (size_t)T + 8 * 16) + 64;
-}
 
 // k-step pairs of one 16-customer tile: SPPT > 0 fully unrolled (static ring
 // slots, so the compiler can count outstanding loads exactly and never drains
@@ -743,9 +738,6 @@ __global__ __launch_bounds__(512) void mvc_par_lpbig_group_kernel(Sweep A, int v
 __global__ void mvc_par_vmax_fill_kernel(double *row, int nb) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nb; i += gridDim.x * blockDim.x) row[i] = -MVC_PM_INF;
 }
-__host__ inline size_t lpbig_shared_bytes(int SP, int NTB, int T, int waves) {
-  return 8 * ((size_t)SP * NTB * 64 + (size_t)waves * 48 + 48 * NTB) + 4 * (32 * NTB + 2 * (size_t)T + (size_t)waves * 16) + 64;
-}
 
 // Generic lp producer: one lane per customer (any D).
 extern "C" __global__ __launch_bounds__(256) void mvc_par_lpgen_kernel(Sweep A, int b0, int nb, double *lpb) {
@@ -833,10 +825,6 @@ __device__ __forceinline__ int pw16_select(const double (&a)[16], double r) {
   return lo;
 }
 
-#define MVC_ZD_NCP 16
-__host__ __device__ inline size_t zdraw_shared_bytes(int V, int T, int sumK) {
-  return 8 * ((size_t)MVC_ZD_NCP * 256 + (size_t)T) + 4 * ((size_t)V * T + (size_t)sumK + (size_t)V + 1) + 64;
-}
 // kSc: the table scores are computed once (one gather pass) into the
 // coalesced scratch sc[p * nb + li] and re-read by the weight and select
 // passes; without it they are re-gathered from the lp buffer in each pass.
@@ -1086,8 +1074,6 @@ __device__ __forceinline__ double zview_sum(const LpRow &row, int koff, int K, i
   return pw16(col);
 }
 
-#define MVC_ZSTAGE 24          // dishes per wave whose lp rows the register draw keeps in LDS (3 blocks/CU)
-
 // The register draw's block-shared tables (LDS).
 struct ZregLds {
   const double *base;    // [TM] log mass of each table (or -inf: excluded)
@@ -1287,10 +1273,6 @@ __global__ __launch_bounds__(256, MVC_ZDRAW_MINB) void mvc_par_zdraw_reg_kernel(
     const uint64_t mv = __ballot(pick != P.z[b0 + li]);
     if (mv && (tid & 63) == (int)__ffsll((long long)mv) - 1) atomicMin(A.fmin, b0 + li);
   }
-}
-__host__ __device__ inline size_t zdraw_reg_shared_bytes(int V, int TM, int sumK) {
-  return 8 * ((size_t)TM + (size_t)sumK + (size_t)4 * MVC_ZSTAGE * 64) +
-         4 * ((size_t)V * TM + (size_t)V + 1 + 2 * MVC_Z_VMAX + (size_t)sumK) + 16;
 }
 
 // Row draw for T > 64 tables (or K_v > 64 dishes): one 16-lane DPP row per
@@ -1511,28 +1493,8 @@ __global__ __launch_bounds__(256, (NB >= 32 || kLds) ? 2 : MVC_ZROW_MINB) void m
     else wave_lds_sync();
   }
 }
-__host__ __device__ inline size_t zdraw_row_shared_bytes(int V, int NB, int sumK, bool lds) {
-  return 8 * ((size_t)16 * NB + 256 + (lds ? (size_t)16 * sumK : 0)) +
-         4 * ((size_t)16 * NB * V + (size_t)V + 1 + (size_t)sumK) + 16;
-}
 
-// ---------------------------------------------------------------------------
-// View patterns (compile-time per-view dish-block counts) of the all-views
-// producer below: bits 0-3 = V, bits 4 + 2 v .. = NT_v - 1 (dish blocks of 16
-// in view v).  Views run in order, unrolled at compile time, so a tile is
-// straight-line code (no joins between views with different NT, which cost
-// the register allocator ~60 VGPRs).  Instances: the bench's K_v = 64, 32,
-// 16, 8 and configs[1]'s 16, 8 shapes, every view count <= 4 with a common
-// dish-block count of 1 or 2, and up to two views of 4 blocks.
-// ---------------------------------------------------------------------------
-#define MVC_FZ_TB 4               // table blocks of 16 (T <= 64)
-#define MVC_FZ_PAT(V, n0, n1, n2, n3) ((V) | (((n0) - 1) << 4) | (((n1) - 1) << 6) | (((n2) - 1) << 8) | (((n3) - 1) << 10))
-#define MVC_FZ_PATS(X)                                                                                     \
-  X(MVC_FZ_PAT(4, 4, 2, 1, 1)) X(MVC_FZ_PAT(3, 4, 2, 1, 1)) X(MVC_FZ_PAT(2, 4, 2, 1, 1))                  \
-  X(MVC_FZ_PAT(2, 2, 1, 1, 1)) X(MVC_FZ_PAT(1, 1, 1, 1, 1)) X(MVC_FZ_PAT(2, 1, 1, 1, 1))                  \
-  X(MVC_FZ_PAT(3, 1, 1, 1, 1)) X(MVC_FZ_PAT(4, 1, 1, 1, 1)) X(MVC_FZ_PAT(1, 2, 2, 2, 2))                  \
-  X(MVC_FZ_PAT(2, 2, 2, 2, 2)) X(MVC_FZ_PAT(3, 2, 2, 2, 2)) X(MVC_FZ_PAT(4, 2, 2, 2, 2))                  \
-  X(MVC_FZ_PAT(1, 4, 4, 4, 4)) X(MVC_FZ_PAT(2, 4, 4, 4, 4)) X(MVC_FZ_PAT(3, 2, 1, 1, 1))
+// the all-views producer's view patterns (MVC_FZ_PATS, mvc_plan.h): bits 0-3 = V, bits 4 + 2 v .. = NT_v - 1
 __host__ __device__ constexpr int fz_pat_v(uint32_t pat) { return (int)(pat & 15u); }
 __host__ __device__ constexpr int fz_pat_nt(uint32_t pat, int v) { return (int)((pat >> (4 + 2 * v)) & 3u) + 1; }
 
@@ -1552,15 +1514,7 @@ struct LpaLds {
   const double *xs, *dens, *cbs;   // per dish: the own-dish coefficient parts (see lpall_self_coef)
   const int *dn, *dl, *tix, *nt, *koff, *boff;
 };
-// Per-wave LDS of the all-views producer: the tile's y2 and h = (-y2/2)/tau
-// per (view, row), the own-dish G and the max over the other included dishes
-// per (view, row) [4][16] each, and the rows' tables [16].
-constexpr int kLpaWaveD = 4 * 4 * 16;   // doubles
-constexpr int kLpaWaveI = 16;           // ints
-__host__ __device__ inline size_t lpall_shared_bytes(size_t s1t_doubles, int V, int sumK, int waves) {
-  return 16 * 4 + 8 * (s1t_doubles + 6 * (size_t)sumK + (size_t)waves * kLpaWaveD) +
-         4 * (2 * (size_t)sumK + (size_t)MVC_FZ_TB * 16 * V + MVC_FZ_TB * 16 + (size_t)waves * kLpaWaveI) + 64;
-}
+// (per-wave LDS kLpaWaveD / kLpaWaveI and lpall_shared_bytes: mvc_plan.h)
 
 // The own-dish coefficient of coef(n - 1, Q', tau, L2pt, D) split into its
 // parts that do not depend on the customer: c0 = X - (0.5 Q') / den with
@@ -1700,12 +1654,6 @@ __device__ __forceinline__ void lpa_views(const Sweep &A, const LpaLds &L, int l
 }
 
 template <int SPPT, int RP, uint32_t PAT>
-#ifndef MVC_LPA_WAVES
-#define MVC_LPA_WAVES 8       // waves per block (one block per CU) of the all-views producer
-#endif
-#ifndef MVC_LPA_RP16
-#define MVC_LPA_RP16 8        // ring depth (k-step pairs in flight per wave) at D = 128
-#endif
 __global__ __launch_bounds__(64 * MVC_LPA_WAVES) void mvc_par_lpall_kernel(Sweep A, int b0, int nb, double *lpb,
                                                                           double *discard) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -2500,21 +2448,6 @@ extern "C" __global__ void mvc_par_snapshot_all_kernel(const SnapArgs *As, int n
 namespace mvc {
 
 namespace {
-constexpr int kParTC = 1 << 18;   // table capacity (three-level tree64 of the MH's global EPPF)
-constexpr int kParKC = (1 << 18) - 1;   // live dishes per view (+1 new element: three-level tree64)
-constexpr size_t kLpbBudget = (size_t)1 << 28;   // phase-1 lp buffer: 2 GiB of doubles per batch
-constexpr int kSeqWaves = 1024;    // waves of the repair eval grid (SeqArgs.G)
-constexpr int kSeqWmin = 1024;     // repair window after a mover
-constexpr int kSeqWmax = 1 << 16;  // cap of the window doubling over mover-free stretches
-constexpr int kSeqRunLimit = 64;   // stays in a row after which the run kernel hands over to grid windows
-constexpr size_t kSeqLdsBudget = 150 * 1024;   // run kernel: per-wave LDS scratch of all its waves
-// the lane-per-customer loop of small chains (mvc_seq_run_kernel<5>): customers,
-// dims, tables (its evaluation's registers) and dishes per view it takes on
-constexpr int kLaneMaxN = 1024, kLaneMaxD = 16, kLaneMaxV = 8, kLaneTM = 32, kLaneMaxK = 32;   // (V: one view per lane of 8)
-constexpr int kWideGridMax = 256;  // grid-wide evaluation: at most this many blocks per customer
-constexpr int kWideBatch = 32;     // grid-wide evaluation: customers (lp + fin pairs) per repair round
-constexpr int kWideFinLds = 152 * 1024;   // the fin kernel's dynamic LDS (wide_fin_resample: dish list, block totals)
-
 template <class Tp>
 Tp *dmalloc(size_t count) {
   void *p = nullptr;
@@ -2561,6 +2494,27 @@ int debug_sync_level() {
 }
 bool debug_sync() { return debug_sync_level() >= 1; }
 
+// ---------------------------------------------------------------------------
+// The templated kernels' instances, one list per family.  A family's launch
+// switch and its dynamic-LDS attributes (set_kernel_attributes) are both
+// generated from its list, so a launched instance cannot lack its attribute.
+// ---------------------------------------------------------------------------
+// mvc_par_lpview_kernel<NT = 1..4, SPPT, RP> and mvc_par_lpall_kernel<SPPT, RP,
+// PAT of MVC_FZ_PATS>: (SPPT, RP), SPPT = SP / 2 k-step pairs per tile (SP is
+// a multiple of 8) unrolled, 0 (last) the runtime loop for every other SP
+#define MVC_LPVIEW_SPPS(X) X(4, 4) X(8, 8) X(16, 8) X(0, 4)
+#define MVC_LPALL_SPPS(X) X(4, 4) X(8, 8) X(16, MVC_LPA_RP16)
+// mvc_par_lpbig_kernel / mvc_par_lpbig_group_kernel<NTB, SPC>
+#define MVC_LPBIG_NTBS(X) X(4) X(2) X(1)
+#define MVC_LPBIG_SPCS(X, NTB) X(NTB, 0) X(NTB, 16) X(NTB, 32) X(NTB, 64)
+// mvc_par_zdraw_row_kernel<NB, slab in LDS>
+#define MVC_ZROW_NBS(X) X(4) X(8) X(16) X(32)
+// mvc_seq_run_kernel<mode> (S: that form only) and mvc_seq_run_kernel_b<mode>
+// (B: both forms): (mode, takes dynamic LDS); mode 2 runs the global-scratch
+// layout only
+#define MVC_RUN_MODES(S, B) B(0, 1) B(2, 0) B(3, 1) B(4, 1) S(5, 1) B(6, 1)
+#define MVC_NONE(...)
+
 class ParallelSampler : public Sampler {
  public:
   int n, V, D, TC, KC, nchunk;
@@ -2602,10 +2556,7 @@ class ParallelSampler : public Sampler {
   double *part1 = nullptr, *part2 = nullptr;
   size_t part_cap = 0;             // sumK capacity of partials
   int32_t *st_host = nullptr;   // pinned [2V+4]: the per-sweep status readback
-  bool force_generic = false;
-  bool force_zdraw_lds = false;   // MVC_PATH zdraw=lds: the LDS-checkpoint draw kernel for every T
-  bool force_zdraw_row = false;   // zdraw=row: the row draw for every T <= 512 (default: 64 < T <= 512)
-  bool no_zrow_lds = false;       // zdraw=row-global: the row draw reads the lp buffer directly
+  PathOpts opts;                  // MVC_PATH, read once in init()
   static constexpr size_t zsc_max_bytes = (size_t)1 << 30;   // the checkpoint draw's table-score scratch limit
   // within-chain N-sharding (mvc_sampler_set_shard): phase A covers this
   // rank's customers only; exch_cb all-gathers the choices into shard_exch
@@ -2614,36 +2565,12 @@ class ParallelSampler : public Sampler {
   int32_t *shard_exch = nullptr;
   int (*shard_cb)(void *) = nullptr;
   void *shard_user = nullptr;
-  bool no_lpall = false;          // MVC_PATH lpall=0: per-view producer launches even where the all-views producer applies
   bool phase_a_only = false;      // sweep_chain stops after phase A (mvc_sampler_phase_a)
   bool phase_a_ran = false;
   int n_cu = 256;
-  bool repair_grid_only = false;  // MVC_PATH repair=grid: every mover through a grid window round (no run kernel)
-  bool force_big = false;         // big=1: the dish-block producer even where the tiled one applies (tests)
-  bool big_runtime_sp = false;    // big_sp=runtime: the dish-block producer's runtime k-step loop only (tests)
-  bool big_group = true;          // big_group=0: one launch per dish block (y re-read per block) instead of the XCD-grouped launch
-  static constexpr int big_bpc_narrow = 3;   // 4-wave blocks per CU of the dish-block producer's 16 / 32-dish instances
-  static constexpr int run_limit = kSeqRunLimit;
-  // waves=N: customers the run kernel evaluates per step.  4 by default:
-  // one evaluating wave per SIMD (a second wave on a SIMD halves the first
-  // customer's issue rate, and with dense movers the first customer decides)
-  int run_waves = 4;
-  bool use_wide = true;           // wide=0: global-scratch run kernel speculates one customer per wave
-  bool wide_grid = true;          // wide=block: the wide evaluation on the run kernel's one block instead of the grid
   double *wide_part = nullptr;    // grid-wide evaluation: per-block partials [kWideGridMax][2V]
-  int wide_fin_lds = kWideFinLds; // the fin kernel's LDS evaluation up to this many bytes (wide_fin=0: off)
-  bool force_global = false;      // run_lds=0: the run kernel's global-scratch layout (tests)
-  bool use_lc = true;             // lc=0: the run kernel's per-wave evaluation without the lane-column form
-  bool use_lane = true;           // lc=col: no lane-per-customer loop for small chains (lane columns instead)
   bool lane_now = false;          // this sweep runs the lane-per-customer loop (sweep_pre)
-  bool use_vp = true;             // vp=0: the lane-column kernel without value prediction
-  // Small chains (n <= small_n_plain, MVC_PATH small_plain=N): the lane-column loop without value
-  // prediction and a stay limit of 16. At the reference's own call (N = 200, V = 5) the
-  // prediction waves' overlay evaluation costs more per step than the steps it saves
-  // (1,578 -> 2,262 sweeps/s, profiles/r5af_*); at N = 1M (the literal) it is worth 1.5x.
-  int small_n_plain = 1024;
   static constexpr int small_first_rounds = 4;   // the first batch of repair rounds of a small chain
-  bool vp_stats = false;          // vp_stats=1: value prediction's steps and hits per sweep on stderr
 
   // MVC_DEBUG_SYNC=1: wait for the launch just made and name it in the error;
   // =2: also read the chain state back and check its invariants (z against
@@ -2656,12 +2583,11 @@ class ParallelSampler : public Sampler {
     const std::string where = std::string(what) + " (chain " + std::to_string(c.gid) + ", sweep " +
                               std::to_string(s) + ", T " + std::to_string(c.T) + ")";
     if (e != hipSuccess) throw Error(MVC_ERR_HIP, "debug sync after " + where + ": " + hipGetErrorString(e));
-    if (debug_level() >= 2) {
+    if (debug_sync_level() >= 2) {
       const std::string bad = check_state(c, rep);
       if (!bad.empty()) throw Error(MVC_ERR_STATE, "state check after " + where + ": " + bad);
     }
   }
-  static int debug_level() { return debug_sync_level(); }
   // Invariants of a chain's state between launches:
   // positions p < T (R->T; table slots are stable within a sweep), dishes
   // j < Klist[v]; every customer in a table, n_t = members, d_l = live tables
@@ -2814,71 +2740,53 @@ class ParallelSampler : public Sampler {
     MVC_HIP(hipHostMalloc((void **)&rs_host, sizeof(Repair), hipHostMallocDefault));
     alloc_seq_scratch();
     std::fill(st_host, st_host + 2 * V + 4, 0);
-    // execution-path overrides (MVC_PATH, tests and A/B runs)
-    force_generic = path_int("generic", 0) == 1;
-    if (const char *e = path_opt("zdraw")) {
-      force_zdraw_lds = std::strcmp(e, "lds") == 0;
-      force_zdraw_row = std::strncmp(e, "row", 3) == 0;
-      no_zrow_lds = std::strcmp(e, "row-global") == 0;
-    }
-    no_lpall = path_int("lpall", 1) == 0;
+    opts = parse_path_opts();   // execution-path overrides (MVC_PATH, tests and A/B runs)
     {
       hipDeviceProp_t prop;
       MVC_HIP(hipGetDeviceProperties(&prop, cf.device));
       n_cu = std::max(1, prop.multiProcessorCount);
     }
-    for (const void *f : {(const void *)mvc_par_zdraw_kernel<true>, (const void *)mvc_par_zdraw_kernel<false>})
-      MVC_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    lpview_attr<4, 4>();
-    lpview_attr<8, 8>();
-    lpview_attr<16, 8>();
-    lpview_attr<0, 4>();
-    MVC_HIP(hipFuncSetAttribute((const void *)mvc_par_stats_partial_kernel,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    lpall_attr<4, 4>();
-    lpall_attr<8, 8>();
-    lpall_attr<16, 8>();
-    // (instance 2 runs the global-scratch layout only: no dynamic LDS)
-    for (const void *f : {(const void *)mvc_seq_run_kernel<0>, (const void *)mvc_seq_run_kernel<3>,
-                          (const void *)mvc_seq_run_kernel<4>, (const void *)mvc_seq_run_kernel<5>,
-                          (const void *)mvc_seq_run_kernel<6>, (const void *)mvc_seq_run_kernel_b<0>,
-                          (const void *)mvc_seq_run_kernel_b<3>, (const void *)mvc_seq_run_kernel_b<4>,
-                          (const void *)mvc_seq_run_kernel_b<6>})
-      MVC_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSeqLdsBudget));   // + the kernel's static LDS <= 160 KB
-    MVC_HIP(hipFuncSetAttribute((const void *)mvc_seq_wide_fin_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kWideFinLds));
-    if (path_int("wide_fin", 1) == 0) wide_fin_lds = 0;   // the global-scratch evaluation
-    if (const char *e = path_opt("repair")) repair_grid_only = std::strcmp(e, "grid") == 0;
-    force_big = path_int("big", 0) == 1;
-    for (const void *f : {(const void *)mvc_par_zdraw_row_kernel<4, true>, (const void *)mvc_par_zdraw_row_kernel<8, true>,
-                          (const void *)mvc_par_zdraw_row_kernel<16, true>, (const void *)mvc_par_zdraw_row_kernel<32, true>})
-      MVC_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-#define MVC_LPBIG_FNS(NTB_)                                                                            \
-  (const void *)mvc_par_lpbig_kernel<NTB_, 0>, (const void *)mvc_par_lpbig_kernel<NTB_, 16>,             \
-      (const void *)mvc_par_lpbig_kernel<NTB_, 32>, (const void *)mvc_par_lpbig_kernel<NTB_, 64>,      \
-      (const void *)mvc_par_lpbig_group_kernel<NTB_, 0>, (const void *)mvc_par_lpbig_group_kernel<NTB_, 16>, \
-      (const void *)mvc_par_lpbig_group_kernel<NTB_, 32>, (const void *)mvc_par_lpbig_group_kernel<NTB_, 64>
-    for (const void *f : {MVC_LPBIG_FNS(4), MVC_LPBIG_FNS(2), MVC_LPBIG_FNS(1)})
-      MVC_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#undef MVC_LPBIG_FNS
-    big_runtime_sp = path_opt("big_sp") && std::strcmp(path_opt("big_sp"), "runtime") == 0;
-    big_group = path_int("big_group", 1) != 0;
-    run_waves = std::max(1, std::min(kSeqRunWaves, path_int("waves", run_waves)));
-    if (const char *e = path_opt("lc")) {   // 0: neither lane-column nor lane loop; col: lane columns only
-      use_lc = e[0] != '0';
-      use_lane = use_lc && e[0] != 'c';
-    }
-    use_vp = path_int("vp", 1) != 0;
-    small_n_plain = path_int("small_plain", small_n_plain);
-    vp_stats = path_int("vp_stats", 0) == 1;
-    if (const char *e = path_opt("wide")) {
-      use_wide = e[0] != '0';
-      wide_grid = e[0] != 'b';
-    }
-    force_global = path_int("run_lds", 1) == 0;
+    set_kernel_attributes();
     chains.resize(cf.n_chains);
     for (int c = 0; c < cf.n_chains; ++c) init_chain(chains[c], chain_gid(cf, c), yh_in);
     MVC_HIP(hipStreamSynchronize(stream));
+  }
+
+  static void max_dynamic_lds(const void *f, int bytes) {
+    MVC_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  }
+  // every instance of the lists above that takes dynamic LDS beyond 64 KB
+  static void set_kernel_attributes() {
+    max_dynamic_lds((const void *)mvc_par_zdraw_kernel<true>, 160 * 1024);
+    max_dynamic_lds((const void *)mvc_par_zdraw_kernel<false>, 160 * 1024);
+#define X(SPPT, RP) lpview_attr<SPPT, RP>();
+    MVC_LPVIEW_SPPS(X)
+#undef X
+    max_dynamic_lds((const void *)mvc_par_stats_partial_kernel, 160 * 1024);
+#define X(SPPT, RP) lpall_attr<SPPT, RP>();
+    MVC_LPALL_SPPS(X)
+#undef X
+#define MVC_RUN_ATTR_1(f) max_dynamic_lds((const void *)f, (int)kSeqLdsBudget);   // + the kernel's static LDS <= 160 KB
+#define MVC_RUN_ATTR_0(f)
+#define X(M, DYN) MVC_RUN_ATTR_##DYN(mvc_seq_run_kernel<M>)
+    MVC_RUN_MODES(X, X)
+#undef X
+#define X(M, DYN) MVC_RUN_ATTR_##DYN(mvc_seq_run_kernel_b<M>)
+    MVC_RUN_MODES(MVC_NONE, X)
+#undef X
+#undef MVC_RUN_ATTR_1
+#undef MVC_RUN_ATTR_0
+    max_dynamic_lds((const void *)mvc_seq_wide_fin_kernel, kWideFinLds);
+#define X(NB) max_dynamic_lds((const void *)mvc_par_zdraw_row_kernel<NB, true>, 80 * 1024);
+    MVC_ZROW_NBS(X)
+#undef X
+#define XB(NTB, SPC) max_dynamic_lds((const void *)mvc_par_lpbig_kernel<NTB, SPC>, 160 * 1024);
+#define XG(NTB, SPC) max_dynamic_lds((const void *)mvc_par_lpbig_group_kernel<NTB, SPC>, 160 * 1024);
+#define X(NTB) MVC_LPBIG_SPCS(XB, NTB) MVC_LPBIG_SPCS(XG, NTB)
+    MVC_LPBIG_NTBS(X)
+#undef X
+#undef XG
+#undef XB
   }
 
   // ---- asynchronous sample output (Sampler::save_async) ----
@@ -3243,11 +3151,7 @@ class ParallelSampler : public Sampler {
     return A;
   }
 
-  // waves per block of the MFMA producer: 4, two blocks per CU = 2 waves per
-  // SIMD.  Measured (scripts/lpv_sweep.py, D = 128, K = 64/32/16/8): more
-  // waves per SIMD only contend for the f64 MFMA pipe and the load queue
-  // (lp 1.11 ms at 4x2, 1.12 at 4x3 / 4x4, 1.22 at 6x2, 1.36 at 2x4).
-  int lpview_waves(int) const { return 4; }
+  // ---- phase A: the launchers of the plan's producer and draw (PhaseAPlan, mvc_plan.h) ----
   template <int SPPT, int RP>
   void launch_lpview_nt(int NT, dim3 grid, dim3 block, size_t lds, const Sweep &A, int v, int b0, int nb) {
     double *disc = lpb + lpb_cap;
@@ -3258,24 +3162,21 @@ class ParallelSampler : public Sampler {
       default: hipLaunchKernelGGL((mvc_par_lpview_kernel<4, SPPT, RP>), grid, block, lds, stream, A, v, b0, nb, lpb, disc); break;
     }
   }
-  // SP (k-steps per tile) is a multiple of 8: pairs per tile SPP = SP / 2
-  void launch_lpview(int NT, dim3 grid, dim3 block, size_t lds, const Sweep &A, int v, int b0, int nb) {
-    switch (SP / 2) {
-      case 4: launch_lpview_nt<4, 4>(NT, grid, block, lds, A, v, b0, nb); break;
-      case 8: launch_lpview_nt<8, 8>(NT, grid, block, lds, A, v, b0, nb); break;
-      case 16: launch_lpview_nt<16, 8>(NT, grid, block, lds, A, v, b0, nb); break;
-      default: launch_lpview_nt<0, 4>(NT, grid, block, lds, A, v, b0, nb); break;
-    }
+  void launch_lpview(int spp, int NT, dim3 grid, dim3 block, size_t lds, const Sweep &A, int v, int b0, int nb) {
+#define X(SPPT, RP) \
+  if (SPPT == 0 || spp == SPPT) return launch_lpview_nt<SPPT, RP>(NT, grid, block, lds, A, v, b0, nb);
+    MVC_LPVIEW_SPPS(X)
+#undef X
   }
   template <int SPPT, int RP>
   static void lpview_attr() {
     for (const void *f : {(const void *)mvc_par_lpview_kernel<1, SPPT, RP>, (const void *)mvc_par_lpview_kernel<2, SPPT, RP>,
                           (const void *)mvc_par_lpview_kernel<3, SPPT, RP>, (const void *)mvc_par_lpview_kernel<4, SPPT, RP>})
-      MVC_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      max_dynamic_lds(f, 160 * 1024);
   }
 
   template <int SPPT, int RP>
-  void launch_lpall(uint32_t pat, dim3 grid, dim3 block, size_t lds, const Sweep &A, int b0, int nb) {
+  void launch_lpall_pat(uint32_t pat, dim3 grid, dim3 block, size_t lds, const Sweep &A, int b0, int nb) {
     double *disc = lpb + lpb_cap;
     switch (pat) {
 #define X(p)                                                                                       \
@@ -3287,243 +3188,103 @@ class ParallelSampler : public Sampler {
       default: throw Error(MVC_ERR_STATE, "all-views producer: no instance for this view pattern");
     }
   }
+  void launch_lpall(int spp, uint32_t pat, dim3 grid, dim3 block, size_t lds, const Sweep &A, int b0, int nb) {
+#define X(SPPT, RP) \
+  if (spp == SPPT) return launch_lpall_pat<SPPT, RP>(pat, grid, block, lds, A, b0, nb);
+    MVC_LPALL_SPPS(X)
+#undef X
+    throw Error(MVC_ERR_STATE, "all-views producer: no instance for this tile depth");
+  }
   template <int SPPT, int RP>
   static void lpall_attr() {
-#define X(p)                                                                                            \
-  MVC_HIP(hipFuncSetAttribute((const void *)mvc_par_lpall_kernel<SPPT, RP, p>,                          \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+#define X(p) max_dynamic_lds((const void *)mvc_par_lpall_kernel<SPPT, RP, p>, 160 * 1024);
     MVC_FZ_PATS(X)
 #undef X
   }
-  void sweep_chain(Chain &c, uint32_t s) {
-    bool phaseA = false;
-    if (sweep_pre(c, s, phaseA)) repair(c, s, phaseA);
-  }
-  // A sweep up to the repair: phase A (producer + draw) of this rank's
-  // customers and, when sharded, the exchange of the choices.  false: the
-  // caller stops here (mvc_sampler_phase_a).
-  bool sweep_pre(Chain &c, uint32_t s, bool &phaseA_out) {
-    // small chains: the run kernel's lane-per-customer loop runs the whole
-    // sweep from customer 0 (its first step is phase A)
-    lane_now = lane_sweep(c);
-    if (!lane_now && c.s1t_stale) {   // after chain-batched lane sweeps (ChainSet::sweep_batched)
-      c.s1t_stale = false;
-      tile_s1(c);
-    }
-    Sweep A = make_sweep(c, s);
-    const SeqArgs Q0 = make_seq(c, s);
-    hipLaunchKernelGGL(mvc_seq_init_kernel, dim3(1), dim3(64), 0, stream, Q0, lane_now ? 1 : 0);
-    MVC_HIP(hipGetLastError());
-    dbg("seq_init", c, s);
-    if (lane_now) {
-      zpath = 32 | 256;
-      phaseA_out = false;
-      return true;
-    }
-    hipEvent_t e0 = nullptr;
-    // phase 1 in customer batches: lp producer (MFMA or generic), then draw
-    int Kmax = 0, Kmin = 1 << 30;
-    for (int k : c.K) { Kmax = std::max(Kmax, k); Kmin = std::min(Kmin, k); }
-    const int sk = sumK(c);
-    const bool use_mfma = !force_generic && !force_big && c.s1t_ok && Kmin >= 1 && Kmax <= MVC_Z_KMAX &&
-                          lpview_shared_bytes(SP, (Kmax + 15) / 16, Kmax, c.T) <= 160 * 1024;
-    // the dish-block MFMA producer (y read directly) where the tiled path does
-    // not apply: the widest dish block whose B-fragments fit, 8 waves per block
-    // (one block per CU) when they take more than half the LDS, else 4 waves
-    // and two blocks per CU -- two waves per SIMD either way
-    const int SPb = ((D / 4 + MVC_ZR - 1) / MVC_ZR) * MVC_ZR;
-    int big_ntb = 0, big_waves = 4;
-    for (int nt : {4, 2, 1}) {
-      if (big_ntb) break;
-      if (lpbig_shared_bytes(SPb, nt, c.T, 4) <= 80 * 1024) { big_ntb = nt; big_waves = 4; }
-      else if (lpbig_shared_bytes(SPb, nt, c.T, 8) <= 150 * 1024) { big_ntb = nt; big_waves = 8; }
-    }
-    const bool use_big = !use_mfma && !force_generic && D % 4 == 0 && D >= 16 && Kmin >= 1 && big_ntb > 0;
-    // batch: multiple of 64 customers, lp buffer <= kLpbBudget doubles
-    const size_t per64 = (size_t)std::max(1, sk) * 64;
-    size_t nb_max = std::max<size_t>(64, (kLpbBudget / per64) * 64);
-    const size_t nb_full = ((size_t)n + 63) / 64 * 64;
-    const size_t nbatch_sz = std::min(nb_max, nb_full);
-    const size_t need = (nbatch_sz / 64) * per64;
-    const bool use_zreg = !force_zdraw_lds && !force_zdraw_row && c.T <= 64 && Kmax <= 64 && sk <= MVC_Z_VMAX * 64 &&
-                          zdraw_reg_shared_bytes(V, 64, sk) <= 64 * 1024;
-    // the row draw (16 lanes per customer) where the register draw does not
-    // apply; lane v of a customer's row holds view v's scalars, so V <= 16
-    const int row_nb = c.T <= 64 ? 4 : c.T <= 128 ? 8 : c.T <= 256 ? 16 : 32;
-    const bool use_zrow = !use_zreg && !force_zdraw_lds && c.T <= 512 && V <= 16 &&
-                          zdraw_row_shared_bytes(V, row_nb, sk, false) <= 64 * 1024;
-    // the row draw with its slab in LDS where two blocks fit a CU
-    const bool zrow_lds = use_zrow && !no_zrow_lds && zdraw_row_shared_bytes(V, row_nb, sk, true) <= 80 * 1024;
-    // phase A on the two-kernel path needs the draw's LDS tables; beyond them
-    // the repair's eval kernel evaluates the sweep from customer 0 instead
-    const bool phaseA = use_zreg || use_zrow || zdraw_shared_bytes(V, c.T, sk) <= 160 * 1024;
-    // the all-views producer: T <= 64, K_v <= 64, every view's S1
-    // B-fragments in LDS at once, fully unrolled k-step pairs
-    size_t s1t_d = 0;
-    for (int v = 0; v < V; ++v) s1t_d += (size_t)SP * 64 * ((c.K[v] + 15) / 16);
-    const int spp = SP / 2;
-    uint32_t fz_pat = (uint32_t)V;
-    for (int v = 0; v < V && v < 4; ++v) fz_pat |= (uint32_t)(std::min(4, (c.K[v] + 15) / 16) - 1) << (4 + 2 * v);
-    bool pat_ok = V <= 4 && Kmax <= 64;
-    switch (pat_ok ? fz_pat : 0u) {
-#define X(p) case p:
-      MVC_FZ_PATS(X)
+  // The dish-block producer: dish block [jb0, jb0 + kb) of view v (first: the
+  // view's first block), or, grouped, all its nblk blocks in one XCD-grouped launch
+  void launch_lpbig(bool grouped, int ntb, int spc, dim3 grid, dim3 block, size_t lds, const Sweep &Ab, int v,
+                    int jb0_or_nblk, int kb, int first, int b0, int nb) {
+    double *disc = lpb + lpb_cap;
+    switch (ntb * 128 + spc) {
+#define X(NTB, SPC)                                                                                                   \
+  case NTB * 128 + SPC:                                                                                               \
+    if (grouped)                                                                                                      \
+      hipLaunchKernelGGL((mvc_par_lpbig_group_kernel<NTB, SPC>), grid, block, lds, stream, Ab, v, jb0_or_nblk, b0, nb, \
+                         lpb, disc);                                                                                  \
+    else                                                                                                              \
+      hipLaunchKernelGGL((mvc_par_lpbig_kernel<NTB, SPC>), grid, block, lds, stream, Ab, v, jb0_or_nblk, kb, first, b0, \
+                         nb, lpb, disc);                                                                              \
+    break;
+#define XN(NTB) MVC_LPBIG_SPCS(X, NTB)
+      MVC_LPBIG_NTBS(XN)
+#undef XN
 #undef X
-      break;
-      default: pat_ok = false;
+      default: throw Error(MVC_ERR_STATE, "dish-block producer: no instance for this block width and tile depth");
     }
-    if (phaseA && need > lpb_cap) {
-      retire(lpb, sizeof(double) * (lpb_cap + 128));
-      lpb_cap = need;
-      lpb = dmalloc<double>(lpb_cap + 128);   // + 128: the producers' per-lane discard slots (16 B per lane)
-    }
-    bool zpath_lpall = false;
-    timers.begin("zresample", &e0);
-    // this rank's customers [lo, hi) (the whole chain unless sharded)
-    const size_t S = (size_t)shard_len(n, shard_world);
-    const size_t lo = std::min((size_t)n, (size_t)shard_rank * S), hi = std::min((size_t)n, lo + S);
-    for (size_t b0 = lo; phaseA && b0 < hi; b0 += nbatch_sz) {
-      const int nb = (int)std::min(nbatch_sz, hi - b0);
-      hipEvent_t el = nullptr, ed = nullptr;
-      timers.begin("lp", &el);
-      const size_t lpa_lds = lpall_shared_bytes(s1t_d, V, sk, MVC_LPA_WAVES);
-      const bool use_lpall = !no_lpall && use_mfma && pat_ok && c.T <= 16 * MVC_FZ_TB &&
-                             (spp == 4 || spp == 8 || spp == 16) && lpa_lds <= 160 * 1024;
-      if (use_lpall) {
-        const int ntile = (nb + 15) / 16;
-        const int grid = std::max(1, std::min(n_cu, (ntile + MVC_LPA_WAVES - 1) / MVC_LPA_WAVES));
-        switch (spp) {
-          case 4: launch_lpall<4, 4>(fz_pat, dim3(grid), dim3(64 * MVC_LPA_WAVES), lpa_lds, A, (int)b0, nb); break;
-          case 8: launch_lpall<8, 8>(fz_pat, dim3(grid), dim3(64 * MVC_LPA_WAVES), lpa_lds, A, (int)b0, nb); break;
-          default: launch_lpall<16, MVC_LPA_RP16>(fz_pat, dim3(grid), dim3(64 * MVC_LPA_WAVES), lpa_lds, A, (int)b0, nb); break;
-        }
-        zpath_lpall = true;
-      } else if (use_mfma) {
-        const int ntile = (nb + 15) / 16;
+  }
+  void launch_producer(const PhaseAPlan &p, const Chain &c, const Sweep &A, int b0, int nb) {
+    switch (p.producer) {
+      case PhaseAPlan::kAllViews:
+        launch_lpall(p.spp, p.fz_pat, dim3(p.producer_grid(0, nb)), dim3(p.producer_threads(0)), p.lpa_lds, A, b0, nb);
+        break;
+      case PhaseAPlan::kPerView:
         for (int v = 0; v < V; ++v) {
-          const int NT = (c.K[v] + 15) / 16;
-          const size_t lds = lpview_shared_bytes(SP, NT, c.K[v], c.T);
-          const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, (160 * 1024) / std::max<size_t>(lds, 1)));
-          const int bw = lpview_waves(NT);
-          const int grid = std::max(1, std::min(per_cu * n_cu, (ntile + bw - 1) / bw));
-          launch_lpview(NT, dim3(grid), dim3(64 * bw), lds, A, v, (int)b0, nb);
+          launch_lpview(p.spp, p.view[v].nt, dim3(p.producer_grid(v, nb)), dim3(p.producer_threads(v)), p.view[v].lds, A,
+                        v, b0, nb);
           MVC_HIP(hipGetLastError());
         }
-      } else if (use_big) {
-        // K_v > 64 or no tiled copy: dish blocks of 16 * NTB, A-fragments from y
-        const int ntile = (nb + 15) / 16;
+        break;
+      case PhaseAPlan::kDishBlock: {
+        Sweep Ab = A;
+        Ab.SP = p.SPb;
         for (int v = 0; v < V; ++v) {
-          // a view with few dishes takes the narrowest block that holds them
-          // (the MFMAs of the padding columns are not issued); the blocks'
-          // lp values and the max-combined view maximum are the same bits
-          // whatever the blocking
-          int vntb = big_ntb;
-          while (vntb > 1 && 16 * (vntb / 2) >= c.K[v]) vntb /= 2;
-          int vwaves = big_waves;
-          if (vntb != big_ntb) vwaves = lpbig_shared_bytes(SPb, vntb, c.T, 4) <= 80 * 1024 ? 4 : 8;
-          const int nblk = (c.K[v] + 16 * vntb - 1) / (16 * vntb);
-          if (big_group && nblk >= 2) {
-            // every dish block of the view in one launch, XCD-grouped (y read once)
-            const size_t lds = lpbig_shared_bytes(SPb, vntb, c.T, vwaves);
-            int per_cu = vwaves == 8 ? 1 : (vntb <= 2 ? big_bpc_narrow : 2);
-            per_cu = std::max(1, std::min<int>(per_cu, (int)((160 * 1024) / std::max<size_t>(lds, 1))));
-            const int grid = per_cu * n_cu;
-            if (n_cu % 8 == 0 && grid / 8 >= nblk) {
-              hipLaunchKernelGGL(mvc_par_vmax_fill_kernel, dim3(std::min(1024, (nb + 255) / 256)), dim3(256), 0, stream,
-                                 A.vmax + (size_t)v * n + b0, nb);
-              Sweep Ab = A;
-              Ab.SP = SPb;
-              const int spc = (4 * SPb == D && !big_runtime_sp && (SPb == 16 || SPb == 32 || SPb == 64)) ? SPb : 0;
-#define MVC_LPBIG(NTB_, SPC_)                                                                                        \
-  hipLaunchKernelGGL((mvc_par_lpbig_group_kernel<NTB_, SPC_>), dim3(grid), dim3(64 * vwaves), lds, stream, Ab, v, nblk, \
-                     (int)b0, nb, lpb, lpb + lpb_cap)
-#define MVC_LPBIG_SP(NTB_)         \
-  switch (spc) {                   \
-    case 16: MVC_LPBIG(NTB_, 16); break; \
-    case 32: MVC_LPBIG(NTB_, 32); break; \
-    case 64: MVC_LPBIG(NTB_, 64); break; \
-    default: MVC_LPBIG(NTB_, 0); break;  \
-  }
-              switch (vntb) {
-                case 4: MVC_LPBIG_SP(4) break;
-                case 2: MVC_LPBIG_SP(2) break;
-                default: MVC_LPBIG_SP(1) break;
-              }
-#undef MVC_LPBIG_SP
-#undef MVC_LPBIG
+          const PhaseAPlan::View &w = p.view[v];
+          const dim3 grid(p.producer_grid(v, nb)), block(p.producer_threads(v));
+          if (w.grouped) {
+            hipLaunchKernelGGL(mvc_par_vmax_fill_kernel, dim3(std::min(1024, (nb + 255) / 256)), dim3(256), 0, stream,
+                               A.vmax + (size_t)v * n + b0, nb);
+            launch_lpbig(true, w.ntb, p.spc, grid, block, w.lds, Ab, v, w.nblk, 0, 0, b0, nb);
+          } else {
+            for (int jb0 = 0, first = 1; jb0 < c.K[v]; jb0 += 16 * w.ntb, first = 0) {
+              launch_lpbig(false, w.ntb, p.spc, grid, block, w.lds, Ab, v, jb0, std::min(16 * w.ntb, c.K[v] - jb0), first,
+                           b0, nb);
               MVC_HIP(hipGetLastError());
-              continue;
             }
           }
-          for (int jb0 = 0, first = 1; jb0 < c.K[v]; jb0 += 16 * vntb, first = 0) {
-            const int kb = std::min(16 * vntb, c.K[v] - jb0);
-            const size_t lds = lpbig_shared_bytes(SPb, vntb, c.T, vwaves);
-            // blocks per CU: the register budget allows three 4-wave blocks of the
-            // narrow instances (<= 168 VGPRs), two of the 64-dish one; LDS permitting
-            int per_cu = vwaves == 8 ? 1 : (vntb <= 2 ? big_bpc_narrow : 2);
-            per_cu = std::max(1, std::min<int>(per_cu, (int)((160 * 1024) / std::max<size_t>(lds, 1))));
-            const int grid = std::max(1, std::min(per_cu * n_cu, (ntile + vwaves - 1) / vwaves));
-            Sweep Ab = A;
-            Ab.SP = SPb;
-            // the unrolled instance where D = 4 SP exactly (no padded k-steps)
-            const int spc = (4 * SPb == D && !big_runtime_sp && (SPb == 16 || SPb == 32 || SPb == 64)) ? SPb : 0;
-#define MVC_LPBIG(NTB_, SPC_)                                                                                   \
-  hipLaunchKernelGGL((mvc_par_lpbig_kernel<NTB_, SPC_>), dim3(grid), dim3(64 * vwaves), lds, stream, Ab, v, jb0, kb, \
-                     first, (int)b0, nb, lpb, lpb + lpb_cap)
-#define MVC_LPBIG_SP(NTB_)         \
-  switch (spc) {                   \
-    case 16: MVC_LPBIG(NTB_, 16); break; \
-    case 32: MVC_LPBIG(NTB_, 32); break; \
-    case 64: MVC_LPBIG(NTB_, 64); break; \
-    default: MVC_LPBIG(NTB_, 0); break;  \
-  }
-            switch (vntb) {
-              case 4: MVC_LPBIG_SP(4) break;
-              case 2: MVC_LPBIG_SP(2) break;
-              default: MVC_LPBIG_SP(1) break;
-            }
-#undef MVC_LPBIG_SP
-#undef MVC_LPBIG
-            MVC_HIP(hipGetLastError());
-          }
+          MVC_HIP(hipGetLastError());
         }
-      } else {
-        hipLaunchKernelGGL(mvc_par_lpgen_kernel, dim3(std::min(4096, (nb + 255) / 256)), dim3(256), 0, stream, A,
-                           (int)b0, nb, lpb);
+        break;
       }
-      MVC_HIP(hipGetLastError());
-      dbg("lp producer", c, s, false);
-      timers.end("lp", el);
-      timers.begin("draw", &ed);
-      const dim3 zg((nb + 255) / 256);   // the register kernel takes one customer per thread
-      // the register draw finds the first mover itself when it sees every customer (no shard)
-      first_in_draw = use_zreg && shard_world == 1;
-      A.fmin = first_in_draw ? &c.R->fmin : nullptr;
-      if (use_zreg && c.T <= 16)
-        hipLaunchKernelGGL(mvc_par_zdraw_reg_kernel<16>, zg, dim3(256), zdraw_reg_shared_bytes(V, 16, sk), stream, A,
-                           (int)b0, nb, (const double *)lpb);
-      else if (use_zreg && c.T <= 32)
-        hipLaunchKernelGGL(mvc_par_zdraw_reg_kernel<32>, zg, dim3(256), zdraw_reg_shared_bytes(V, 32, sk), stream, A,
-                           (int)b0, nb, (const double *)lpb);
-      else if (use_zreg)
-        hipLaunchKernelGGL(mvc_par_zdraw_reg_kernel<64>, zg, dim3(256), zdraw_reg_shared_bytes(V, 64, sk), stream, A,
-                           (int)b0, nb, (const double *)lpb);
-      else if (use_zrow) {
-        // 16 customers (one slab) per block and round
-        const dim3 rg(std::max(1, std::min((nb + 15) / 16, (zrow_lds ? 2 : 8) * n_cu)));
-        const size_t rl = zdraw_row_shared_bytes(V, row_nb, sk, zrow_lds);
-        const double *lc = lpb;
-#define MVC_ZROW(NBV)                                                                                      \
-  if (zrow_lds) hipLaunchKernelGGL((mvc_par_zdraw_row_kernel<NBV, true>), rg, dim3(256), rl, stream, A, (int)b0, nb, lc); \
-  else hipLaunchKernelGGL((mvc_par_zdraw_row_kernel<NBV, false>), rg, dim3(256), rl, stream, A, (int)b0, nb, lc);
-        switch (row_nb) {
-          case 4: MVC_ZROW(4) break;
-          case 8: MVC_ZROW(8) break;
-          case 16: MVC_ZROW(16) break;
-          default: MVC_ZROW(32) break;
+      case PhaseAPlan::kGeneric:
+        hipLaunchKernelGGL(mvc_par_lpgen_kernel, dim3(p.producer_grid(0, nb)), dim3(p.producer_threads(0)), 0, stream, A,
+                           b0, nb, lpb);
+        break;
+    }
+  }
+  void launch_draw(const PhaseAPlan &p, const Chain &c, const Sweep &A, int b0, int nb) {
+    const dim3 grid(p.draw_grid(nb)), block(256);
+    const double *lc = lpb;
+    switch (p.draw) {
+      case PhaseAPlan::kReg:
+        switch (p.reg_tm) {
+          case 16: hipLaunchKernelGGL(mvc_par_zdraw_reg_kernel<16>, grid, block, p.draw_lds, stream, A, b0, nb, lc); break;
+          case 32: hipLaunchKernelGGL(mvc_par_zdraw_reg_kernel<32>, grid, block, p.draw_lds, stream, A, b0, nb, lc); break;
+          default: hipLaunchKernelGGL(mvc_par_zdraw_reg_kernel<64>, grid, block, p.draw_lds, stream, A, b0, nb, lc); break;
         }
-#undef MVC_ZROW
-      } else {
+        break;
+      case PhaseAPlan::kRow:
+        switch (p.row_nb) {
+#define X(NB)                                                                                                         \
+  case NB:                                                                                                            \
+    if (p.row_lds) hipLaunchKernelGGL((mvc_par_zdraw_row_kernel<NB, true>), grid, block, p.draw_lds, stream, A, b0, nb, lc); \
+    else hipLaunchKernelGGL((mvc_par_zdraw_row_kernel<NB, false>), grid, block, p.draw_lds, stream, A, b0, nb, lc);   \
+    break;
+          MVC_ZROW_NBS(X)
+#undef X
+        }
+        break;
+      case PhaseAPlan::kCheckpoint: {
         // the table-score scratch (T x nb doubles) when it stays under 1 GiB
         const size_t scn = (size_t)c.T * (size_t)nb;
         const bool use_sc = scn * sizeof(double) <= zsc_max_bytes;
@@ -3532,31 +3293,91 @@ class ParallelSampler : public Sampler {
           zsc_cap = scn + scn / 2;
           zsc = dmalloc<double>(zsc_cap);
         }
-        if (use_sc)
-          hipLaunchKernelGGL(mvc_par_zdraw_kernel<true>, dim3(std::min(4096, (nb + 255) / 256)), dim3(256),
-                             zdraw_shared_bytes(V, c.T, sk), stream, A, (int)b0, nb, (const double *)lpb, zsc);
-        else
-          hipLaunchKernelGGL(mvc_par_zdraw_kernel<false>, dim3(std::min(4096, (nb + 255) / 256)), dim3(256),
-                             zdraw_shared_bytes(V, c.T, sk), stream, A, (int)b0, nb, (const double *)lpb, zsc);
+        if (use_sc) hipLaunchKernelGGL(mvc_par_zdraw_kernel<true>, grid, block, p.draw_lds, stream, A, b0, nb, lc, zsc);
+        else hipLaunchKernelGGL(mvc_par_zdraw_kernel<false>, grid, block, p.draw_lds, stream, A, b0, nb, lc, zsc);
+        break;
       }
+    }
+  }
+
+  // the shape the plans depend on (mvc_plan.h), from the chain's host mirror of T and K_v
+  Shape shape_of(const Chain &c) const {
+    Shape s;
+    s.n = n; s.V = V; s.D = D;
+    s.SP = SP;
+    s.s1t_ok = c.s1t_ok;
+    s.T = c.T;
+    std::copy(c.K.begin(), c.K.end(), s.K);
+    s.n_cu = n_cu;
+    const int64_t S = shard_len(n, shard_world);
+    s.lo = std::min<int64_t>(n, shard_rank * S);
+    s.hi = std::min<int64_t>(n, s.lo + S);
+    s.sharded = shard_world > 1;
+    s.phase_a_only = phase_a_only;
+    return s;
+  }
+
+  void sweep_chain(Chain &c, uint32_t s) {
+    bool phaseA = false;
+    if (sweep_pre(c, s, phaseA)) repair(c, s, phaseA);
+  }
+  // A sweep up to the repair: plan phase A, grow its buffers, then per batch
+  // of this rank's customers the producer and the draw; when sharded, the
+  // exchange of the choices.  false: the caller stops here (mvc_sampler_phase_a).
+  bool sweep_pre(Chain &c, uint32_t s, bool &phaseA_out) {
+    Shape sh = shape_of(c);
+    if (c.s1t_stale && !lane_sweep(sh, opts)) {   // leaving the lane loop (whose sweeps do not re-tile S1): phase A reads S1t
+      tile_s1(c);
+      sh.s1t_ok = c.s1t_ok;
+    }
+    const PhaseAPlan p = plan_phase_a(sh, opts);
+    lane_now = p.lane;
+    Sweep A = make_sweep(c, s);
+    const SeqArgs Q0 = make_seq(c, s);
+    hipLaunchKernelGGL(mvc_seq_init_kernel, dim3(1), dim3(64), 0, stream, Q0, lane_now ? 1 : 0);
+    MVC_HIP(hipGetLastError());
+    dbg("seq_init", c, s);
+    if (p.lane) {
+      zpath = p.zpath();
+      phaseA_out = false;
+      return true;
+    }
+    hipEvent_t e0 = nullptr;
+    if (p.run && p.lpb_need > lpb_cap) {
+      retire(lpb, sizeof(double) * (lpb_cap + 128));
+      lpb_cap = p.lpb_need;
+      lpb = dmalloc<double>(lpb_cap + 128);   // + 128: the producers' per-lane discard slots (16 B per lane)
+    }
+    timers.begin("zresample", &e0);
+    for (int64_t b0 = p.lo; p.run && b0 < p.hi; b0 += (int64_t)p.batch) {
+      const int nb = (int)std::min<int64_t>((int64_t)p.batch, p.hi - b0);
+      hipEvent_t el = nullptr, ed = nullptr;
+      timers.begin("lp", &el);
+      launch_producer(p, c, A, (int)b0, nb);
+      MVC_HIP(hipGetLastError());
+      dbg("lp producer", c, s, false);
+      timers.end("lp", el);
+      timers.begin("draw", &ed);
+      first_in_draw = p.first_in_draw;
+      A.fmin = first_in_draw ? &c.R->fmin : nullptr;
+      launch_draw(p, c, A, (int)b0, nb);
       MVC_HIP(hipGetLastError());
       dbg("z draw", c, s, false);
       timers.end("draw", ed);
     }
     timers.end("zresample", e0);
     if (phase_a_only) {                            // mvc_sampler_phase_a: the pass alone
-      phase_a_ran = phaseA;
-      zpath = phaseA ? ((use_mfma ? 2 : 0) | (use_zreg ? 4 : 0) | (zpath_lpall ? 16 : 0) | (use_big ? 64 : 0) |
-                        (use_zrow ? 128 : 0)) : 32;
+      phase_a_ran = p.run;
+      zpath = p.zpath();
       return false;
     }
-    if (phaseA && shard_world > 1) {
+    if (p.run && shard_world > 1) {
       // the other ranks' phase-A choices: this shard into the exchange buffer,
       // the caller's all-gather (synchronous), every shard back.  Each rank
       // then runs the same repair on the same state: no other exchange.
-      if (hi > lo)
-        MVC_HIP(hipMemcpyAsync(shard_exch + lo, c.choice + lo, (hi - lo) * sizeof(int32_t), hipMemcpyDeviceToDevice,
-                               stream));
+      if (p.hi > p.lo)
+        MVC_HIP(hipMemcpyAsync(shard_exch + p.lo, c.choice + p.lo, (p.hi - p.lo) * sizeof(int32_t),
+                               hipMemcpyDeviceToDevice, stream));
       MVC_HIP(hipStreamSynchronize(stream));
       // a failed exchange stops the sweep here: nothing has read the buffer
       // and phase A changed no chain state (only choice / lp / vmax)
@@ -3564,126 +3385,13 @@ class ParallelSampler : public Sampler {
         throw Error(MVC_ERR_CALLBACK, "set_shard: the all_gather callback reported failure; the sweep was not run");
       MVC_HIP(hipMemcpyAsync(c.choice, shard_exch, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
     }
-    zpath = phaseA ? ((use_mfma ? 2 : 0) | (use_zreg ? 4 : 0) | (zpath_lpall ? 16 : 0) |
-                      (use_big ? 64 : 0) | (use_zrow ? 128 : 0)) : 32;
-    phaseA_out = phaseA;
+    zpath = p.zpath();
+    phaseA_out = p.run;
     return true;
   }
-
-  // The small chains' lane-per-customer loop (mvc_seq_run_kernel<5>, L.lc ==
-  // 3): the state cache with S1, tables up to kLaneTM (the evaluation's
-  // registers), dish lists with room to double, and a ring holding the whole
-  // sweep's rows; no per-wave scratch.  L.lc == 0: it does not fit.
-  SeqLds lane_layout(int T, const int32_t *Klist) const {
-    int kmax = 1;
-    for (int v = 0; v < V; ++v) kmax = std::max(kmax, (int)Klist[v]);
-    SeqLds L{};
-    L.limit = kNoWindows;
-    L.ks = (kmax + std::max(16, kmax) + 15) / 32 * 32 + 16;
-    L.ts = kLaneTM;
-    L.s1 = 1;
-    L.cache_dbl = seq_lds_cache(V, D, L.ks, L.ts, true);
-    L.stride = 0;
-    L.nws = kSeqLcThreads / 64;
-    int rn = 2;
-    while (rn < n) rn *= 2;
-    if (T >= L.ts || 8 * (L.cache_dbl + (int64_t)rn * seq_ring_slot(V, D)) > (int64_t)kSeqLdsBudget) return L;
-    L.lds = 1;
-    L.tw = 1;
-    L.ring = rn;
-    L.pfn = 0;
-    L.vpo = 0;
-    L.lc = 3;
-    L.small = (T <= kLaneSmall && kmax <= kLaneSmall) ? 1 : 0;
-    return L;
-  }
-  // the layout of a repair round: the lane loop while this sweep runs it and
-  // the state still fits it, else the run kernels' (run_layout)
-  SeqLds pick_layout(int T, const int32_t *Klist, bool vp_ok) const {
-    if (lane_now) {
-      bool ok = T < kLaneTM;
-      for (int v = 0; v < V; ++v) ok = ok && Klist[v] <= kLaneMaxK;
-      if (ok) {
-        const SeqLds L = lane_layout(T, Klist);
-        if (L.lc == 3) return L;
-      }
-    }
-    return run_layout(T, Klist, vp_ok);
-  }
-  bool lane_sweep(const Chain &c) const {
-    if (!use_lane || force_global || repair_grid_only || phase_a_only || shard_world > 1) return false;
-    if (n > kLaneMaxN || D > kLaneMaxD || V > kLaneMaxV || c.T >= kLaneTM) return false;
-    for (int k : c.K)
-      if (k > kLaneMaxK) return false;
-    return lane_layout(c.T, c.K.data()).lc == 3;
-  }
-
-  // LDS layout of the run kernel's per-wave scratch for T tables and dish
-  // lists Klist, with room for growth (a birth past it makes the kernel exit
-  // with R->restride; the host then relaunches with a new layout).  Falls back
-  // to the per-wave global scratch when even a few waves do not fit.
-  SeqLds run_layout(int T, const int32_t *Klist, bool vp_ok = true) const {
-    int kmax = 1;
-    for (int v = 0; v < V; ++v) kmax = std::max(kmax, (int)Klist[v]);
-    SeqLds L{};
-    // small chains: the run kernel walks the whole sweep (a window round is a
-    // launch triple and a host read-back, more than the steps it saves)
-    L.limit = n <= small_n_plain ? 16 : run_limit;
-    // in order of preference: S1 cached with room to double (a cold sweep's
-    // births then rarely restride; in a chain batch a restride ends the round
-    // for every chain), S1 cached with room to grow by half, then without S1,
-    // then tight margins without S1
-    for (int attempt = force_global ? 4 : 0; attempt < 4; ++attempt) {
-      const bool s1 = attempt <= 1;
-      const int kgrow = attempt == 0 ? std::max(16, kmax) : attempt < 3 ? std::max(8, kmax / 2) : 4;
-      const int tgrow = attempt == 0 ? std::max(128, T) : attempt < 3 ? std::max(64, T / 2) : 16;
-      // ks = 16 (mod 32): the lane-column evaluation's rows (views) read dish
-      // j of [v][ks] arrays at v ks + j, so rows 0 / 1 (and 2 / 3) of a
-      // ds_read_b64 lane group then fall on disjoint banks (2 ks dwords = 32
-      // mod 64), and of a ds_read_b32 too (ks = 16 mod 32)
-      L.ks = (kmax + kgrow + 15) / 32 * 32 + 16;
-      L.ts = (T + tgrow + 63) / 64 * 64;   // whole 64-table chunks (the lane-column evaluation's e[] scratch)
-      if (attempt == 0 && use_lc && L.ts > 64 * kLcChunks) continue;   // doubling would leave the lane-column form
-      L.s1 = s1 ? 1 : 0;
-      L.cache_dbl = seq_lds_cache(V, D, L.ks, L.ts, s1);
-      L.stride = seq_lds_stride(V, D, L.ks, L.ts);
-      const int64_t room = (int64_t)kSeqLdsBudget / 8 - L.cache_dbl;
-      const int cap = run_waves;   // customers per step
-      L.nws = room > 0 ? (int)std::min<int64_t>(cap, room / L.stride) : 0;
-      if (L.nws >= std::min(cap, s1 ? 4 : 2)) {
-        L.lds = 1;
-        L.tw = 1;
-        L.lc = 0;   // the lane-column kernel needs the ring (set below)
-        // the staged-row ring in what is left: a power of two >= 2 nws customers
-        const int64_t slot = seq_ring_slot(V, D);
-        const int64_t left = room - (int64_t)L.nws * L.stride;
-        int rn = 0;
-        for (int r = 256; r >= 2 * L.nws; r >>= 1)
-          if ((int64_t)r * slot <= left) { rn = r; break; }
-        L.ring = rn;
-        L.pfn = rn ? std::max(1, rn / 2) : 0;
-        L.lc = (use_lc && s1 && rn > 0 && L.ts <= 64 * kLcChunks) ? 1 : 0;
-        if (L.lc) L.nws = std::min(L.nws, kSeqLcThreads / 64);   // its block has 4 waves
-        // value prediction (lc == 2) where its overlay fits: V <= kVpV, every dish list <= 128, and the
-        // overlay's S1 columns [kVpE][D] after the ring (which follows the clamped nws scratches)
-        L.vpo = L.cache_dbl + (int64_t)L.nws * L.stride + (int64_t)rn * slot;
-        if (L.lc && use_vp && vp_ok && n > small_n_plain && V <= kVpV && kmax <= 128 && L.nws >= kSeqLcThreads / 64 &&
-            left - (int64_t)rn * slot >= (int64_t)kVpE * D)
-          L.lc = 2;
-        return L;
-      }
-    }
-    L.lds = 0;   // per-wave global scratch (SeqScratch(A, w)): capacity-sized, never restrides
-    L.lc = 0;
-    // the whole block on one customer (seq_resample_wide): the dish / table
-    // lists are long here, and where the state outgrows the LDS nearly every
-    // customer moves (cold-start transients), so speculation buys little
-    L.tw = use_wide ? kSeqRunWaves : 1;
-    L.s1 = 0;
-    L.nws = use_wide ? 1 : run_waves;
-    L.stride = 0;
-    L.cache_dbl = 0;
-    return L;
+  // the layout of a repair round for T tables and dish lists Klist (pick_layout, mvc_plan.h)
+  SeqLds pick_layout(const Chain &c, int T, const int32_t *Klist, bool vp_ok) const {
+    return mvc::pick_layout(shape_of(c), opts, lane_now, T, Klist, vp_ok);
   }
 
   // Phase A's choices are exact up to the first customer that does not stay;
@@ -3721,31 +3429,45 @@ class ParallelSampler : public Sampler {
     MVC_HIP(hipGetLastError());
     dbg("seq_first / eval", c, s);
     rr.vp_ok = true;   // value prediction until it stops itself in this sweep (R->vpoff)
-    rr.L = pick_layout(c.T, c.K.data(), rr.vp_ok);
+    rr.L = pick_layout(c, c.T, c.K.data(), rr.vp_ok);
     // the gated early MH (below) only where no per-phase timers bracket the
     // repair and the MH separately (they would time the MH as repair)
     // (not for small chains: nearly every sweep of theirs moves someone, so the
     // gated launch would be a no-op launch per sweep)
-    rr.early_mh = allow_early_mh && (!timers.on || timers.coarse) && n > small_n_plain;
+    rr.early_mh = allow_early_mh && (!timers.on || timers.coarse) && n > opts.small_n_plain;
     if (rr.early_mh && !rs_ev) MVC_HIP(hipEventCreateWithFlags(&rs_ev, hipEventDisableTiming));
     // the first batch of rounds: one; small chains four (their repair
     // usually takes 2-5 rounds, and a batch costs a host round trip)
-    rr.rounds = (n <= small_n_plain && !lane_now) ? small_first_rounds : 1;
+    rr.rounds = (n <= opts.small_n_plain && !lane_now) ? small_first_rounds : 1;
   }
-  // The run kernel's dynamic LDS for layout L.
-  int64_t run_dyn(const SeqLds &L) const {
-    return L.lds ? 8 * (L.cache_dbl + L.stride * L.nws + (int64_t)L.ring * seq_ring_slot(V, D) +
-                        (L.lc == 2 ? (int64_t)kVpE * D : 0))
-                 : 0;
+  // The run kernel of instance ri (run_instance, mvc_plan.h) on stream st: one
+  // chain's (a, l: its arguments and layout on the host) or, batched, one block
+  // per chain of the device arrays a, l
+  static void launch_run(const RunInstance &ri, bool batched, dim3 grid, size_t dyn, hipStream_t st, const SeqArgs *a,
+                         const SeqLds *l) {
+    const dim3 block(ri.threads);
+    if (!batched) {
+      switch (ri.mode) {
+#define X(M, DYN) case M: hipLaunchKernelGGL(mvc_seq_run_kernel<M>, grid, block, dyn, st, *a, *l); return;
+        MVC_RUN_MODES(X, X)
+#undef X
+      }
+    } else {
+      switch (ri.mode) {
+#define X(M, DYN) case M: hipLaunchKernelGGL(mvc_seq_run_kernel_b<M>, grid, block, dyn, st, a, l); return;
+        MVC_RUN_MODES(MVC_NONE, X)
+#undef X
+      }
+    }
+    throw Error(MVC_ERR_STATE, std::string("run kernel: no instance ") + ri.name + (batched ? " (batched)" : ""));
   }
-  // The grid-wide evaluation where the state is on the global layout (L.lds = 0) and
-  // the block-wide evaluation applies (L.tw > 1): one customer over many CUs
-  bool run_wgrid(const SeqLds &L) const { return !repair_grid_only && wide_grid && L.lds == 0 && L.tw > 1; }
   // rr.rounds repair rounds of one chain on its stream
   void repair_rounds(Chain &c, uint32_t s, RepairRun &rr) {
     const dim3 eb(256);
     SeqLds &L = rr.L;
-    const bool wgrid = run_wgrid(L);
+    const bool repair_grid_only = opts.repair_grid_only;
+    const bool wgrid = run_wgrid(opts, L);
+    const RunInstance ri = run_instance(L, false);
     int wblk = 1;
     if (wgrid) {
       if (!wide_part) wide_part = dmalloc<double>((size_t)kWideGridMax * 2 * V);
@@ -3762,13 +3484,13 @@ class ParallelSampler : public Sampler {
         hipLaunchKernelGGL(mvc_seq_wide_begin_kernel, dim3(1), dim3(64), 0, stream, rr.Q);
         for (int b = 0; b < kWideBatch; ++b) {
           hipLaunchKernelGGL(mvc_seq_wide_lp_kernel, dim3(wblk), dim3(kWideGridThreads), 0, stream, rr.Q, wide_part);
-          hipLaunchKernelGGL(mvc_seq_wide_fin_kernel, dim3(1), dim3(kSeqRunThreads), wide_fin_lds, stream, rr.Q,
-                             (const double *)wide_part, wblk, L.limit, wide_fin_lds);
+          hipLaunchKernelGGL(mvc_seq_wide_fin_kernel, dim3(1), dim3(kSeqRunThreads), opts.wide_fin_lds, stream, rr.Q,
+                             (const double *)wide_part, wblk, L.limit, opts.wide_fin_lds);
         }
         MVC_HIP(hipGetLastError());
         dbg("seq_wide (begin + lp/fin pairs)", c, s);
       } else {
-        L.dyn = run_dyn(L);
+        L.dyn = run_dyn(V, D, L);
         L.fill = lds_fill_byte();
         L.chk = run_check() ? 1 : 0;
         if (L.lc == 3 && L.small && (rr.birth_retry || (rr.birth_between && r > 0))) {
@@ -3778,14 +3500,10 @@ class ParallelSampler : public Sampler {
           MVC_HIP(hipGetLastError());
           dbg("seq_birth", c, s);
         }
-        hipLaunchKernelGGL(L.lc ? (L.lc == 3 ? (L.small ? mvc_seq_run_kernel<5> : mvc_seq_run_kernel<6>)
-                                             : L.lc == 2 ? mvc_seq_run_kernel<4> : mvc_seq_run_kernel<3>)
-                                : L.tw == 1 ? mvc_seq_run_kernel<0> : mvc_seq_run_kernel<2>,
-                           dim3(1), dim3(L.lc == 3 && L.small ? kLaneSmallThreads : L.lc ? kSeqLcThreads : kSeqRunThreads),
-                           (size_t)L.dyn, stream, rr.Q, L);
+        launch_run(ri, false, dim3(1), (size_t)L.dyn, stream, &rr.Q, &L);
       }
       MVC_HIP(hipGetLastError());
-      dbg(repair_grid_only ? "seq_apply" : L.lc == 3 ? (L.small ? "seq_run<5>" : "seq_run<6>") : L.lc == 2 ? "seq_run<4>" : L.lc ? "seq_run<3>" : L.tw == 1 ? "seq_run<0>" : "seq_run<2>", c, s);
+      dbg(repair_grid_only ? "seq_apply" : ri.name, c, s);
       if (L.lc && !(L.lc == 3 && L.small) && !repair_grid_only && rr.birth_retry) {   // a birth the loop left pending (births commit in the kernel)
         rr.birth_retry = false;
         hipLaunchKernelGGL(mvc_seq_birth_kernel, dim3(1), dim3(kSeqRunThreads), 0, stream, rr.Q);
@@ -3822,7 +3540,7 @@ class ParallelSampler : public Sampler {
       if (rr.L.lc == 2) rr.L.lc = 1;
     }
     if (rs.restride) {
-      rr.L = pick_layout(rs.T, rs.Klist, rr.vp_ok);
+      rr.L = pick_layout(c, rs.T, rs.Klist, rr.vp_ok);
       MVC_HIP(hipMemsetAsync(&c.R->restride, 0, sizeof(int32_t), stream));
       return 0;
     }
@@ -3864,12 +3582,9 @@ class ParallelSampler : public Sampler {
               rs.prof[20]);
     }
 #endif
-    if (vp_stats)   // MVC_VP_STATS=1: value prediction's steps and full hits of this sweep, on stderr
+    if (opts.vp_stats)   // value prediction's steps and full hits of this sweep, on stderr
       fprintf(stderr, "mvc vp steps %d hits %d off %d\n", rs.vpsteps, rs.vphits, rs.vpoff);
-    c.last[0] = rs.moves;
-    c.last[1] = rs.births;
-    c.last[2] = rs.rounds;
-    c.last[3] = rs.newdish;
+    note_outcome(c, rs);
     if (!(rr.early_mh && !moved)) launch_hyper(c, 1, s);   // else the gated launch above ran it
     if (moved) {   // new T and dish counts for the next sweep's launch shapes
       MVC_HIP(hipMemcpyAsync(st_host, c.status, sizeof(int32_t) * (2 * V + 4), hipMemcpyDeviceToHost, stream));
@@ -3877,15 +3592,30 @@ class ParallelSampler : public Sampler {
       else status_pending = true;
     }
   }
+  // a finished sweep's repair counters (repair_stats)
+  static void note_outcome(Chain &c, const Repair &rs) {
+    c.last[0] = rs.moves;
+    c.last[1] = rs.births;
+    c.last[2] = rs.rounds;
+    c.last[3] = rs.newdish;
+  }
+  // after a sweep with moves: T and the dish counts of the next sweep's launch
+  // shapes from the status row read back.  S1 changed: its tiling (the next
+  // phase A's MFMA B-fragments) is rebuilt now, or marked stale and rebuilt
+  // when the chain leaves the lane loop, whose sweeps do not read it
+  void take_status(Chain &c, const int32_t *row, bool retile_now) {
+    c.T = row[0];
+    for (int v = 0; v < V; ++v) c.K[v] = row[1 + v];
+    if (retile_now) tile_s1(c);
+    else c.s1t_stale = true;
+  }
   bool status_pending = false;
   Repair last_rs{};                // the chain-batched sweep's final outcome of this chain
   // the next sweep's launch shapes from the status copied back by repair_finish
   void repair_status(Chain &c) {
     MVC_HIP(hipStreamSynchronize(stream));
     status_pending = false;
-    c.T = st_host[0];
-    for (int v = 0; v < V; ++v) c.K[v] = st_host[1 + v];
-    tile_s1(c);   // S1 changed: the next phase A's MFMA B-fragments
+    take_status(c, st_host, true);
   }
   void repair(Chain &c, uint32_t s, bool phaseA) {
     RepairRun rr;
@@ -3945,16 +3675,9 @@ class ParallelSampler : public Sampler {
     }
     const Repair &rs = *rs_host;
     timers.end("repair", rr.e1);
-    if (vp_stats) fprintf(stderr, "mvc vp steps %d hits %d off %d\n", rs.vpsteps, rs.vphits, rs.vpoff);
-    c.last[0] = rs.moves;
-    c.last[1] = rs.births;
-    c.last[2] = rs.rounds;
-    c.last[3] = rs.newdish;
-    if (rs.moves > 0) {   // new T and dish counts for the next sweep's launch shapes (S1t: s1t_stale)
-      c.T = st_host[0];
-      for (int v = 0; v < V; ++v) c.K[v] = st_host[1 + v];
-      c.s1t_stale = true;
-    }
+    if (opts.vp_stats) fprintf(stderr, "mvc vp steps %d hits %d off %d\n", rs.vpsteps, rs.vphits, rs.vpoff);
+    note_outcome(c, rs);
+    if (rs.moves > 0) take_status(c, st_host, false);
   }
 
   // Double the table (flags & 1) and/or dish (flags & 2) capacity of every
@@ -3963,9 +3686,8 @@ class ParallelSampler : public Sampler {
   // is redone.
   void grow_capacity(int flags) {
     // the table limit: the MH's three-level tree64 over the table sizes
-    // (64^3 = 262,144); MVC_MAX_TABLES lowers it (tests of the limit's error)
-    int max_tc = kParTC;
-    max_tc = std::max(16, std::min(kParTC, path_int("max_tables", kParTC)));
+    // (64^3 = 262,144); MVC_PATH max_tables lowers it (tests of the limit's error)
+    const int max_tc = opts.max_tables;
     const int TC2 = (flags & 1) ? std::min(max_tc, 2 * TC) : TC;
     const int KC2 = (flags & 2) ? std::min(kParKC, 2 * KC + 1) : KC;
     if (TC2 == TC && KC2 == KC)
@@ -4260,9 +3982,7 @@ class ChainSet : public Sampler {
   // and the MH of every chain on its stream.  The same kernels run on the same
   // state as a chain swept alone, so every chain is the same chain, bit for bit;
   // concurrency no longer needs a hardware queue per chain.
-  bool batch_on = [] {
-    return path_int("chain_batch", 1) != 0;   // chain_batch=0: one host thread and stream per chain
-  }();
+  const bool batch_on = parse_path_opts().chain_batch;   // MVC_PATH chain_batch=0: one host thread per chain
   SeqArgs *bA_dev = nullptr, *bA_host = nullptr, *bE_dev = nullptr, *bE_host = nullptr;
   SeqLds *bL_dev = nullptr, *bL_host = nullptr;
   Repair *bR_dev = nullptr, *bR_host = nullptr;
@@ -4329,7 +4049,7 @@ class ChainSet : public Sampler {
     bool lane_batch = (!tm.on || tm.coarse) && debug_sync_level() == 0;
     for (int c = 0; c < C && lane_batch; ++c) {
       ParallelSampler &S = *subs[c];
-      lane_batch = !S.repair_grid_only && S.lane_sweep(S.chains[0]);
+      lane_batch = lane_sweep(S.shape_of(S.chains[0]), S.opts);
     }
     if (!lane_batch && last_lane_batch) {   // the chains' streams after the batch stream's last sweep and saves
       MVC_HIP(hipEventRecord(b_join, bs));
@@ -4349,7 +4069,7 @@ class ChainSet : public Sampler {
         auto &ch = S.chains[0];
         const uint32_t s = (uint32_t)S.sweeps_done;
         S.lane_now = true;
-        S.zpath = 32 | 256;
+        S.zpath = kZpathLane;
         S.repair_start(ch, s, false, rr[c], false);   // (host only for a lane sweep)
         bI_host[c] = rr[c].Q;
       }
@@ -4382,38 +4102,33 @@ class ChainSet : public Sampler {
         rounds = std::max(rounds, rr[c].rounds);
         bpc = std::min(bpc, std::max(1, rr[c].Q.G / 4));
       }
-      // the instances: 4 / 3 lane columns (+ value prediction), 0 one wave per
-      // customer, 2 the block-wide evaluation; -1 launched per chain (grid-wide
-      // evaluation, grid-only repair)
+      // the batched run-kernel modes (run_instance, mvc_plan.h); -1 launched per
+      // chain (grid-wide evaluation, grid-only repair)
       std::vector<int> kinds(C, -1);
       for (int c : act) {
         const ParallelSampler &S = *subs[c];
         const SeqLds &L = rr[c].L;
-        // (lane loops batched in the general instance <6>: births commit in the kernel)
-        kinds[c] = (S.repair_grid_only || S.run_wgrid(L)) ? -1 : L.lc == 3 ? 6 : L.lc == 2 ? 4 : L.lc ? 3 : L.tw == 1 ? 0 : 2;
+        kinds[c] = (S.opts.repair_grid_only || run_wgrid(S.opts, L)) ? -1 : run_instance(L, true).mode;
       }
       int nb = 0;   // batched members, grouped by kind
-      std::vector<std::pair<int, int>> groups;   // (kind, first index), each up to the next
-      std::vector<size_t> dyn;
+      struct Group { RunInstance ri; int first; size_t dyn; };   // members from first up to the next group's
+      std::vector<Group> groups;
       for (int k : {6, 4, 3, 0, 2}) {
-        const int first = nb;
-        size_t dmax = 0;
+        Group g{RunInstance{}, nb, 0};
         for (int c : act) {
           if (kinds[c] != k) continue;
           ParallelSampler &S = *subs[c];
           SeqLds &L = rr[c].L;
-          L.dyn = S.run_dyn(L);
+          L.dyn = run_dyn(S.V, S.D, L);
           L.fill = lds_fill_byte();
           L.chk = run_check() ? 1 : 0;
           bA_host[nb] = rr[c].Q;
           bL_host[nb] = L;
-          dmax = std::max(dmax, (size_t)L.dyn);
+          g.ri = run_instance(L, true);
+          g.dyn = std::max(g.dyn, (size_t)L.dyn);
           ++nb;
         }
-        if (nb > first) {
-          groups.push_back({k, first});
-          dyn.push_back(dmax);
-        }
+        if (nb > g.first) groups.push_back(g);
       }
       // every active chain's arguments for the outcome gather, the batched
       // chains first: only they take part in the batched window evaluation
@@ -4445,18 +4160,9 @@ class ChainSet : public Sampler {
       if (any_single) MVC_HIP(hipEventRecord(b_join, bs));
       for (int r = 0; r < rounds; ++r) {
         for (size_t g = 0; g < groups.size(); ++g) {
-          const int k = groups[g].first, f = groups[g].second;
-          const int m = (g + 1 < groups.size() ? groups[g + 1].second : nb) - f;
-          const dim3 grid(m);
-          const SeqArgs *a = bA_dev + f;
-          const SeqLds *l = bL_dev + f;
-          switch (k) {
-            case 6: hipLaunchKernelGGL(mvc_seq_run_kernel_b<6>, grid, dim3(kSeqLcThreads), dyn[g], bs, a, l); break;
-            case 4: hipLaunchKernelGGL(mvc_seq_run_kernel_b<4>, grid, dim3(kSeqLcThreads), dyn[g], bs, a, l); break;
-            case 3: hipLaunchKernelGGL(mvc_seq_run_kernel_b<3>, grid, dim3(kSeqLcThreads), dyn[g], bs, a, l); break;
-            case 0: hipLaunchKernelGGL(mvc_seq_run_kernel_b<0>, grid, dim3(kSeqRunThreads), dyn[g], bs, a, l); break;
-            default: hipLaunchKernelGGL(mvc_seq_run_kernel_b<2>, grid, dim3(kSeqRunThreads), dyn[g], bs, a, l); break;
-          }
+          const int f = groups[g].first;
+          const int m = (g + 1 < groups.size() ? groups[g + 1].first : nb) - f;
+          ParallelSampler::launch_run(groups[g].ri, true, dim3(m), groups[g].dyn, bs, bA_dev + f, bL_dev + f);
           MVC_HIP(hipGetLastError());
         }
         if (n_bat) {
@@ -4517,18 +4223,8 @@ class ChainSet : public Sampler {
           done[c] = 1;
           S.last_rs = bR_host[j];
           if (lane_batch) {   // the outcome, and the next sweep's shapes from the status row
-            auto &ch = S.chains[0];
-            const Repair &rs = bR_host[j];
-            ch.last[0] = rs.moves;
-            ch.last[1] = rs.births;
-            ch.last[2] = rs.rounds;
-            ch.last[3] = rs.newdish;
-            if (rs.moves > 0) {
-              const int32_t *st = bS_host + j * SL;
-              ch.T = st[0];
-              for (int v = 0; v < cfg.n_views; ++v) ch.K[v] = st[1 + v];
-              ch.s1t_stale = true;   // (S1t, only read by a phase A, is re-tiled when the chain leaves the lane loop)
-            }
+            S.note_outcome(S.chains[0], bR_host[j]);
+            if (bR_host[j].moves > 0) S.take_status(S.chains[0], bS_host + j * SL, false);
           }
         } else if (res == 0) {
           MVC_HIP(hipStreamSynchronize(S.stream));   // (a relayout's reset on the chain's stream)
@@ -4696,13 +4392,13 @@ class ChainSet : public Sampler {
 };
 
 Sampler *make_parallel_sampler_device(const mvc_config &cfg, DeviceData &&dd) {
-  if (cfg.n_chains > 1 && path_int("chain_threads", 1) != 0) return new ChainSet(cfg, std::move(dd));
+  if (cfg.n_chains > 1 && parse_path_opts().chain_threads) return new ChainSet(cfg, std::move(dd));
   return new ParallelSampler(cfg, std::move(dd));
 }
 
 Sampler *make_parallel_sampler(const mvc_config &cfg, const double *const *views) {
   // chain_threads=0 (MVC_PATH): one handle runs its chains one after another
-  if (cfg.n_chains > 1 && path_int("chain_threads", 1) != 0) return new ChainSet(cfg, views);
+  if (cfg.n_chains > 1 && parse_path_opts().chain_threads) return new ChainSet(cfg, views);
   return new ParallelSampler(cfg, views);
 }
 

@@ -49,8 +49,6 @@ struct Repair {
                                 // [20] / [21] its wall ticks / shader clocks from decision start to exit (the effective clock)
 };
 
-constexpr int32_t kSeqScan = 0, kSeqRun = 1;
-
 // MVC_RUN_PROF builds (scripts/build_variant.sh NAME -DMVC_RUN_PROF): thread 0
 // of the run kernel accumulates wall-clock ticks (100 MHz) per phase in LDS
 // (no global read-modify-write inside the timed phases) and adds them to
@@ -64,39 +62,7 @@ __shared__ unsigned long long mvc_prof_lds[12];
 #define RUN_T0() do {} while (0)
 #define RUN_MARK(k) do {} while (0)
 #endif
-// run kernel block: 8 waves (256 VGPRs each: the per-customer evaluation
-// spills at the 128 VGPRs of a 16-wave block)
-constexpr int kSeqRunThreads = 512, kSeqRunWaves = kSeqRunThreads / 64;
-// the lane-column run kernel: 4 waves, one per SIMD (its evaluation is issue-
-// bound; a second wave per SIMD would halve the first customer's rate)
-constexpr int kSeqLcThreads = 256;
-// the small chains' lane loop (mvc_seq_run_kernel<5>): 8 waves, two per SIMD,
-// 64 customers per step (its registers allow it; the general lane kernel <6>
-// and the lane-column kernels keep 4 waves)
-constexpr int kLaneSmallThreads = 512;
-
-// LDS layout of the run kernel's per-wave scratch (host-chosen at launch):
-// lp [V][ks] | e [ts + 16] | B, C [ts/16 + 2]; nws waves speculate.
-// lds = 0: the per-wave global scratch (SeqArgs.scr) instead.
-// LDS of the run kernel: the state cache (SCache: n_t [ts], dish [V][ts],
-// d_l, d_n [V][ks], Klist, Ltot [V], T, T_ne; c0, cb, Q, xm, ym, cbm [V][ks];
-// lmass [ts]; S1T [V][D][ks] when s1) and the per-wave scratch (SeqScratch).
-struct SeqLds {
-  int32_t lds, nws, ks, ts;
-  int32_t limit;        // stays in a row after which the run kernel hands over to the grid windows
-  int32_t s1;           // S1 cached in LDS
-  int64_t cache_dbl;    // doubles of the state cache (the per-wave scratch follows)
-  int64_t stride;       // doubles per wave
-  int32_t ring;         // customers in the staged-row ring (power of 2, after the per-wave scratch; 0: none)
-  int32_t pfn;          // customers prefetched into the ring per step
-  int32_t tw;           // waves per customer (1: seq_resample; kSeqRunWaves: seq_resample_wide); nws customers per step
-  int32_t lc;           // 1: the lane-column evaluation (seq_resample_lc; LDS layout with S1 cached, ts <= 512); 2: + value prediction
-  int64_t vpo;          // lc == 2: offset (doubles) of the overlay's S1 columns [kVpE][D] in the dynamic LDS
-  int64_t dyn;          // bytes of dynamic LDS of the launch
-  int32_t small;        // lc == 3: every dish list and the tables <= kLaneSmall (mvc_seq_run_kernel<5>)
-  int32_t fill;         // MVC_LDS_FILL diagnostics: >= 0 fills the block's LDS with this byte at launch
-  int32_t chk;          // MVC_RUN_CHECK diagnostics: check every index a commit writes through (R->dbg)
-};
+// (block shapes, SeqLds and its size functions: mvc_plan.h)
 
 // MVC_RUN_CHECK: the first failed index check of the run kernel's block
 // (code, then up to 7 values); a failed check skips the write it guards and
@@ -112,22 +78,6 @@ __device__ __forceinline__ bool run_chk(bool ok, int code, int a = 0, int b = 0,
   }
   return false;
 }
-// ring slot: y rows [V][D], Y2 [V], z (as a double)
-__host__ __device__ inline int64_t seq_ring_slot(int V, int D) { return (int64_t)V * D + V + 1; }
-
-// lp row stride of the LDS scratch: the lane-column evaluation stores dish j
-// of a row at j + j / 32 (lc_lpx), so the table gathers of dishes j and j + 32
-// (the same bank of ds_read_b64 otherwise) fall on different banks
-__host__ __device__ inline int seq_lps(int ks) { return ks + (ks >> 5) + 1; }
-__host__ __device__ inline int64_t seq_lds_stride(int V, int D, int ks, int ts) {
-  // lp [V][seq_lps] | aux [V][ks] | e | B, C | mv | koff | ys [V][D] + Y2 [V] + lm_v [V] + member maxima [4]
-  return (int64_t)V * seq_lps(ks) + (int64_t)V * ks + ts + 16 + ts / 16 + 2 + V + V + 2 + (int64_t)V * D + V + V + 4;
-}
-__host__ __device__ inline int64_t seq_lds_cache(int V, int D, int ks, int ts, bool s1) {
-  const int64_t ints = (int64_t)ts + (int64_t)V * ts + 2 * (int64_t)V * ks + 2 * V + 2;
-  return (ints + 1) / 2 + 7 * (int64_t)V * ks + ts + (s1 ? (int64_t)V * D * ks : 0);
-}
-
 struct SeqArgs {
   ParState P;
   const double *y;        // [V][n][D]
@@ -1074,7 +1024,6 @@ __device__ __forceinline__ double row_bcast_d(double x) { return dpp_d<0x150 + k
 // then decides customers up to the first whose decision differs from its
 // prediction: every one of them was evaluated against the state the
 // sequential schedule has at its turn.
-constexpr int kVpMoves = 4, kVpV = 8, kVpE = kVpMoves * kVpV * 2;
 struct VpOv {
   int nm;                                      // predicted customers in the overlay (i .. i+nm-1)
   int mv[kVpMoves], p0[kVpMoves], c[kVpMoves]; // mv: customer i+m is a predicted move p0 -> c
@@ -1470,7 +1419,6 @@ __device__ __forceinline__ void lc_scores_weights(const SView &W, const SeqScrat
 // scratch, block sums by row pw16, running block totals in lane b (b < 64)
 // so the draw finds its block with one ballot.  hyp / cnewv: the sweep's
 // hyperparameters and new-dish constants, staged in LDS at kernel launch.
-constexpr int kLcChunks = 8;   // tables <= 512 (block totals in lanes b < 64 need TB <= 64)
 template <bool kVp = false>
 __device__ __forceinline__ int seq_resample_lc(const SeqArgs &A, const SView &W, const Cust &C, int i, int p0, const SeqScratch &S,
                                const double *hyp, const double *cnewv, const VpCtx &X = VpCtx{}) {
@@ -2251,7 +2199,6 @@ __device__ __forceinline__ void note_mover(int32_t &lastm, int32_t &gapq, int f)
   gapq = (3 * gapq + 16 * gap) >> 2;
   lastm = f;
 }
-constexpr int kNoWindows = 1 << 29;   // a limit this large: the run kernel never hands over to windows
 __device__ __forceinline__ int stay_limit(int limit, int gapq) {
   return (limit < kNoWindows && gapq > 16 * kSparseGap) ? min(limit, kSparseLimit) : limit;
 }
@@ -2363,7 +2310,6 @@ extern "C" __global__ __launch_bounds__(kSeqRunThreads) void mvc_seq_birth_kerne
 // decisions are the oracle's bit for bit; only the partition of the
 // order-free max / count over the dishes differs.
 // ---------------------------------------------------------------------------
-constexpr int kWideGridThreads = 256;
 extern "C" __global__ void mvc_seq_wide_begin_kernel(SeqArgs A) {
   if (threadIdx.x != 0) return;
   Repair *R = A.R;
@@ -3848,7 +3794,6 @@ __device__ __forceinline__ int seq_run_loop_vp(SeqArgs &A, const SeqLds &L, cons
 // log(alpha_v + L_v - 1) (the own table dies), k = 2V / 2V + 1 log(ag + sg
 // T_ne) / log(ag + sg (T_ne - 1)), k = 2V + 2 + p log((n_p - 1) - sg) (the
 // own table without the customer).  Needs 2V + 2 + T <= 64 (V <= 8, T < 32).
-constexpr int kLanePre = 64;   // 2V + 2 + T <= 64 (V <= 8, T < 32)
 __shared__ double mvc_lane_pre[kLaneSmallThreads / 64][kLanePre];
 struct LanePre {
   const double *pre;   // this wave's row
@@ -4228,7 +4173,6 @@ constexpr int lane_cust() { return (kSmall ? kLaneSmallThreads : kSeqLcThreads) 
 // one straight-line evaluation instance and no birth commit in the kernel
 // (a birth ends the launch; mvc_seq_birth_kernel commits it), so the loop's
 // registers are the small evaluation's (a larger state exits with restride).
-constexpr int kLaneSmall = 8;
 template <bool kSmall>
 __device__ __forceinline__ int seq_run_loop_lane(SeqArgs &A, const SeqLds &L, const Ring &G, RunCursor &U) {
   constexpr int kW = (kSmall ? kLaneSmallThreads : kSeqLcThreads) / 64;
