@@ -119,6 +119,17 @@ int mvc_result_copy_chain(const mvc_result *r, int chain, int32_t *table_of, int
  * and the Gelman-Rubin potential scale reduction (NaN with fewer than two
  * chains or two saved samples).  Either pointer may be NULL. */
 int mvc_result_summary(const mvc_result *r, double *mean, double *rhat);
+/* Cluster labels of every chain's saved samples, labels[(C*S)*n] chain-major
+ * (row c*S + s), gathered on the run's first device: level MVC_LEVEL_TABLES
+ * is table_of as it is (the global partition); level v in [0, V) is
+ * dish_of[v][table_of[i]], the clusters of view v that get_final_clusters
+ * (New_Simulation.R:135-149) derives for the last sample, here for every
+ * one.  Each sample's raw dish ids are renumbered 0..K-1 in ascending raw id
+ * before the gather (the same partition; tight label ranges for
+ * mvc_partition_compare).  No reference counterpart in the C++: the
+ * caller's step in R.  MVC_ERR_ARG: NULL argument, level outside [-1, V). */
+#define MVC_LEVEL_TABLES (-1)
+int mvc_result_labels(const mvc_result *r, int level, int32_t *labels, char *err, size_t errlen);
 void mvc_result_free(mvc_result *r);
 
 /* ------------------------------------------------------------------------ */
@@ -240,6 +251,46 @@ void mvc_sampler_destroy(mvc_sampler *s);
 /* Adjusted Rand index of two host label arrays a[n], b[n] on the device
  * (same computation as mvc_sampler_ari). */
 int mvc_ari(int device, const int32_t *a, const int32_t *b, int64_t n, double *ari, char *err, size_t errlen);
+
+/* ------------------------------------------------------------------------ */
+/* Posterior clustering summary of S draws of a labeling of n items           */
+/* (labels[S][n], HOST array, any int32 values; ranges are taken per draw).   */
+/* No reference counterpart in the C++; the caller's mcclust / mcclust.ext    */
+/* step after run_gibbs_cpp (New_Simulation.R:5-7 loads them, :189 scores     */
+/* only the last draw).  Computed on the device (mvc_posterior.hip).          */
+/* ------------------------------------------------------------------------ */
+#define MVC_POSTERIOR_MAX_DRAWS 8192     /* S cap of mvc_partition_compare: each S x S output <= 512 MiB */
+#define MVC_POSTERIOR_PSM_MAX_N 16384    /* n cap of mvc_partition_psm: 1 GiB of counts                  */
+#define MVC_POSTERIOR_LDS_CELLS 32768    /* a pair with ra*rb + ra + rb cells beyond this (128 KiB of
+                                            LDS) is counted in global scratch instead; same results    */
+/* Pairwise distances of the draws, expected losses and their argmins.  For
+ * draws s, t with contingency table n_ij (margins n_i., n_.j):
+ *   binder[s*S+t] = sum C(n_i.,2) + sum C(n_.j,2) - 2 sum C(n_ij,2), the number
+ *     of item pairs on which the two draws disagree (exact);
+ *   vi[s*S+t] = ((sum n_i. ln n_i. + sum n_.j ln n_.j) - 2 sum n_ij ln n_ij)
+ *     / n / ln 2, the variation of information in bits (mcclust.ext::VI), the
+ *     sums in fp64 in a fixed order (equal inputs give equal bits);
+ *   both symmetric with a diagonal of 0 by definition;
+ *   binder_sum[s] = sum_t binder[s*S+t] (exact), vi_sum[s] = sum_t vi[s*S+t]
+ *     added in ascending t; divide by S for the expected loss of draw s;
+ *   best[0] = argmin binder_sum: mcclust::minbinder(method = "draws");
+ *   best[1] = argmin vi_sum: the exact posterior expected VI over the draws,
+ *     not the lower bound mcclust.ext::minVI(method = "draws") minimises;
+ *   ties go to the lowest index.
+ * binder[S*S], vi[S*S], binder_sum[S], vi_sum[S], best[2]; any output may be
+ * NULL.  S = 1 and n = 1 are legal (all distances 0).  MVC_ERR_ARG: labels
+ * NULL, S < 1, n < 1, S > MVC_POSTERIOR_MAX_DRAWS.  MVC_ERR_UNSUPPORTED: a
+ * pair of draws with range_s * range_t > 2^26 contingency cells. */
+int mvc_partition_compare(int device, const int32_t *labels, int64_t S, int64_t n,
+                          uint64_t *binder, double *vi, uint64_t *binder_sum, double *vi_sum,
+                          int32_t *best, char *err, size_t errlen);
+/* Co-clustering counts[n*n]: the number of draws in which items i and j share
+ * a label (exact; symmetric, diagonal S).  counts / S is the posterior
+ * similarity matrix of mcclust::comp.psm.  MVC_ERR_ARG: labels NULL, S < 1,
+ * n < 1, counts NULL.  MVC_ERR_UNSUPPORTED: n > MVC_POSTERIOR_PSM_MAX_N,
+ * reported before counts is looked at or anything is allocated. */
+int mvc_partition_psm(int device, const int32_t *labels, int64_t S, int64_t n,
+                      uint32_t *counts, char *err, size_t errlen);
 int mvc_device_math(int device, int op, const double *x, double *out, int64_t n,
                     char *err, size_t errlen);
 int mvc_device_seq_uniforms(int device, uint64_t seed, uint32_t chain, uint64_t start,

@@ -16,6 +16,7 @@
 
 #include "mvc.h"
 #include "mvc_host.h"
+#include "mvc_posterior_host.h"
 
 namespace mvc {
 
@@ -359,6 +360,7 @@ void run_part(const mvc_config &cf, const double *const *views, RunPart &R) {
 
 struct mvc_result {
   int S = 0, C = 0, n = 0, V = 0;
+  int device = 0;   // the run's first device (mvc_result_labels gathers there)
   // [chain] flat, as RunPart: table_of S x n, dish_of the [V][T_s] blocks at doff[chain][s]
   std::vector<std::vector<int32_t>> table_of, dish_of;
   std::vector<std::vector<size_t>> doff;
@@ -488,6 +490,64 @@ int mvc_ari(int device, const int32_t *a, const int32_t *b, int64_t n, double *a
       throw;
     }
     hipFree(d);
+  });
+}
+
+int mvc_partition_compare(int device, const int32_t *labels, int64_t S, int64_t n, uint64_t *binder, double *vi,
+                          uint64_t *binder_sum, double *vi_sum, int32_t *best, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    if (!labels) throw mvc::Error(MVC_ERR_ARG, "partition_compare: labels is NULL");
+    if (S < 1) throw mvc::Error(MVC_ERR_ARG, "partition_compare: S must be >= 1");
+    if (n < 1) throw mvc::Error(MVC_ERR_ARG, "partition_compare: n must be >= 1");
+    if (S > mvc::kPostMaxDraws)
+      throw mvc::Error(MVC_ERR_ARG, "partition_compare: S above MVC_POSTERIOR_MAX_DRAWS (" +
+                                        std::to_string(mvc::kPostMaxDraws) + ")");
+    mvc::partition_compare(device, labels, S, n, binder, vi, binder_sum, vi_sum, best);
+  });
+}
+
+int mvc_partition_psm(int device, const int32_t *labels, int64_t S, int64_t n, uint32_t *counts, char *err,
+                      size_t errlen) {
+  return guarded(err, errlen, [&] {
+    if (!labels) throw mvc::Error(MVC_ERR_ARG, "partition_psm: labels is NULL");
+    if (S < 1) throw mvc::Error(MVC_ERR_ARG, "partition_psm: S must be >= 1");
+    if (n < 1) throw mvc::Error(MVC_ERR_ARG, "partition_psm: n must be >= 1");
+    if (n > mvc::kPostPsmMaxN)
+      throw mvc::Error(MVC_ERR_UNSUPPORTED, "partition_psm: n above MVC_POSTERIOR_PSM_MAX_N (" +
+                                                std::to_string(mvc::kPostPsmMaxN) + "): the counts exceed 1 GiB");
+    if (!counts) throw mvc::Error(MVC_ERR_ARG, "partition_psm: counts is NULL");
+    mvc::partition_psm(device, labels, S, n, counts);
+  });
+}
+
+int mvc_result_labels(const mvc_result *r, int level, int32_t *labels, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    if (!r) throw mvc::Error(MVC_ERR_ARG, "result_labels: result is NULL");
+    if (!labels) throw mvc::Error(MVC_ERR_ARG, "result_labels: labels is NULL");
+    if (level < MVC_LEVEL_TABLES || level >= r->V)
+      throw mvc::Error(MVC_ERR_ARG, "result_labels: level must be MVC_LEVEL_TABLES or a view in [0, " +
+                                        std::to_string(r->V) + ")");
+    const size_t block = (size_t)r->S * r->n;
+    if (block == 0) return;
+    if (level == MVC_LEVEL_TABLES) {
+      for (int c = 0; c < r->C; ++c) std::copy(r->table_of[c].begin(), r->table_of[c].end(), labels + c * block);
+      return;
+    }
+    // view `level`: each sample's dish ids compacted on the host (T_s entries), the n-long gather on the device
+    std::vector<int32_t> table((size_t)r->C * block), dish;
+    std::vector<int64_t> off;
+    off.push_back(0);
+    for (int c = 0; c < r->C; ++c) {
+      std::copy(r->table_of[c].begin(), r->table_of[c].end(), table.begin() + c * block);
+      for (int s = 0; s < r->S; ++s) {
+        const int T = r->T[c][s];
+        const int32_t *raw = r->dish_of[c].data() + r->doff[c][s] + (size_t)level * T;
+        dish.resize(dish.size() + T);
+        mvc::compact_ids(raw, T, dish.data() + off.back());
+        off.push_back(off.back() + T);
+      }
+    }
+    mvc::gather_labels(r->device, table.data(), (int64_t)r->C * r->S, r->n, dish, off, labels);
   });
 }
 
@@ -642,6 +702,7 @@ int mvc_run(const mvc_config *cfg, const double *const *views, mvc_result **out,
     R->C = C;
     R->n = cfg->n;
     R->V = V;
+    R->device = dmap.empty() ? cfg->device : dmap[0];
     R->S = parts[0].S;
     for (int c = 0; c < C; ++c) {
       RunPart &P = parts[c % nd];

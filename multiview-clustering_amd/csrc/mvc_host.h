@@ -177,6 +177,16 @@ class Sampler {
 double ari_device(const int32_t *da, const int32_t *db, int64_t n, hipStream_t stream);
 double ari_from_pairs(uint64_t a, uint64_t sa, uint64_t sb, int64_t n);
 
+// Posterior clustering summary (mvc_posterior.hip): host arrays in and out,
+// computed on `device`.  labels[S][n]; outputs as mvc_partition_compare /
+// mvc_partition_psm (any compare output may be NULL).
+void partition_compare(int device, const int32_t *labels, int64_t S, int64_t n, uint64_t *binder, double *vi,
+                       uint64_t *binder_sum, double *vi_sum, int32_t *best);
+void partition_psm(int device, const int32_t *labels, int64_t S, int64_t n, uint32_t *counts);
+// out[r][i] = dish[off[r] + table_of[r][i]] for R samples (off has R + 1 entries).
+void gather_labels(int device, const int32_t *table_of, int64_t R, int64_t n, const std::vector<int32_t> &dish,
+                   const std::vector<int64_t> &off, int32_t *out);
+
 // Global id of a handle's local chain c (mvc_config.chain_stride): the id
 // keys every Philox counter of the chain.
 inline uint32_t chain_gid(const mvc_config &c, int local) {

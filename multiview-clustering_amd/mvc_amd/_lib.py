@@ -21,7 +21,13 @@ TRACE_ALPHA_V, TRACE_SIGMA_V, TRACE_TAU_V, TRACE_ALPHA_GLOBAL, TRACE_SIGMA_GLOBA
 
 
 ABI_VERSION = 2
+MVC_ERR_ARG = 1
+MVC_ERR_UNSUPPORTED = 4
 MVC_ERR_CALLBACK = 5
+LEVEL_TABLES = -1                 # mvc_result_labels: the global (table) partition
+POSTERIOR_MAX_DRAWS = 8192        # MVC_POSTERIOR_MAX_DRAWS
+POSTERIOR_PSM_MAX_N = 16384       # MVC_POSTERIOR_PSM_MAX_N
+POSTERIOR_LDS_CELLS = 32768       # MVC_POSTERIOR_LDS_CELLS
 
 # all_gather callback of mvc_sampler_set_shard: int (*)(void *user), 0 = done
 SHARD_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p)
@@ -92,6 +98,7 @@ def lib():
         "mvc_result_trace": (dp, [vp, i32, i32]),
         "mvc_result_copy_chain": (i32, [vp, i32, ip, ip, ip]),
         "mvc_result_summary": (i32, [vp, dp, dp]),
+        "mvc_result_labels": (i32, [vp, i32, ip, cp, sz]),
         "mvc_result_free": (None, [vp]),
         "mvc_sampler_create": (i32, [cfgp, ctypes.POINTER(dp), vpp, cp, sz]),
         "mvc_sampler_sweep": (i32, [vp, i32, cp, sz]),
@@ -109,6 +116,9 @@ def lib():
         "mvc_sampler_set_timing": (i32, [vp, i32]),
         "mvc_sampler_ari": (i32, [vp, i32, ip, dp, cp, sz]),
         "mvc_ari": (i32, [i32, ip, ip, i64, dp, cp, sz]),
+        "mvc_partition_compare": (i32, [i32, ip, i64, i64, ctypes.POINTER(u64), dp, ctypes.POINTER(u64), dp, ip,
+                                        cp, sz]),
+        "mvc_partition_psm": (i32, [i32, ip, i64, i64, ctypes.POINTER(u32), cp, sz]),
         "mvc_sampler_stream": (vp, [vp]),
         "mvc_sampler_create_synthetic": (i32, [cfgp, ctypes.c_int32, u64, ctypes.c_double, ctypes.c_double, ip, vpp,
                                                cp, sz]),

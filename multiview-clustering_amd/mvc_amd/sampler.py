@@ -121,7 +121,7 @@ def _view_ptrs(y):
 
 
 def run_gibbs_cpp(data_views, M, burn_in, thin, seed=1999, mode="exact", n_chains=1, device=0,
-                  first_chain=0, quiet=False, n_devices=1, summary=None, timing=None):
+                  first_chain=0, quiet=False, n_devices=1, summary=None, timing=None, labels=None):
     """Drop-in for the reference's ``run_gibbs_cpp`` (see module docstring).
 
     With ``n_chains > 1`` a list of per-chain result dicts is returned; the
@@ -131,7 +131,11 @@ def run_gibbs_cpp(data_views, M, burn_in, thin, seed=1999, mode="exact", n_chain
     (mvc_result_summary: keys ``mean`` and ``rhat``, float64[3V+2] in the
     order tau_v, alpha_v, sigma_v, alpha_global, sigma_global).  ``timing``
     (a dict) receives ``mvc_run_s``, the seconds of the library call alone
-    (the rest is building these Python lists).
+    (the rest is building these Python lists).  ``labels`` (a dict) receives
+    the cluster labels of every chain's saved samples, gathered on the device
+    (mvc_result_labels): key -1 the table partition, key v the clusters of
+    view v with each sample's dish ids renumbered 0..K-1, each int32
+    [n_chains * S, n] chain-major (``posterior.draws(res, v, compact=True)``).
     """
     y = _views_to_array(data_views)
     V, n, D = y.shape
@@ -151,6 +155,12 @@ def run_gibbs_cpp(data_views, M, burn_in, thin, seed=1999, mode="exact", n_chain
             dp = ctypes.POINTER(ctypes.c_double)
             lib.mvc_result_summary(res, mean.ctypes.data_as(dp), rhat.ctypes.data_as(dp))
             summary["mean"], summary["rhat"] = mean, rhat
+        if labels is not None:
+            for level in range(L.LEVEL_TABLES, V):
+                lab = np.empty((n_chains * S, n), dtype=np.int32)
+                L.check(lib.mvc_result_labels(res, level, lab.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), buf,
+                                              len(buf)), buf)
+                labels[level] = lab
         outs = []
         ip = ctypes.POINTER(ctypes.c_int32)
         for c in range(n_chains):
